@@ -3,7 +3,11 @@
 
 One "step" = one pass of the hot path over one batch of synthetic requests:
     ViT-L/14 (224 px) -> Resampler -> projection -> splice -> LLaMA-7B prefill (T=128) -> 128-token greedy decode.
-Four workloads are timed per default run (SURVEY.md section 8d "two regimes, report both"; every leg carries BOTH images/sec definitions:
+A plain run times the main workload only: set-up, --warmup steps, EXACTLY --steps timed steps, the result line (`value`, `ms_per_step`).
+`--dump-outputs DIR` writes what the last timed step returned (the generated ids, as float64) to DIR/tokens.npy; model and inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
+Everything below that is not the main workload's timed steps runs with `--full` only (the stage breakdown, the other legs, the rooflines,
+the CPU baseline).  Four workloads are timed per --full run (SURVEY.md section 8d "two regimes, report both"; every leg carries BOTH images/sec definitions:
 `images_per_sec` = whole requests, `images_per_sec_prefill` = images through ViT + Resampler + projection + prefill):
   * configs[1] -- `value`: B = 1 request per GPU (BASELINE.json configs[1]; the latency / HBM-bound regime), EXACTLY --steps steps;
   * configs[2] -- `images_per_sec`, `config2`: B = 64 requests per GPU (BASELINE.json configs[2]; ViT + Resampler throughput,
@@ -20,7 +24,7 @@ batch is sharded by rank (weak scaling: per-GPU batch fixed), the only collectiv
 per step, inside the timed region.  `--plumbing-check` runs the same launch / shard / gather / max-over-ranks path on CPU
 (gloo) with a token-pattern stand-in for the model: tests/test_host_cpu.py uses it; it measures nothing.
 
-Prints ONE JSON line on rank 0: throughput, `roofline` (the dominant kernel of the timed configs[1] workload, HBM regime),
+Prints ONE JSON line on rank 0: throughput, and with --full `breakdown_ms`, `roofline` (the dominant kernel of the timed configs[1] workload, HBM regime),
 `rooflines` (all regimes: whole-step decode bytes vs 8 TB/s for B = 1 and B = 64, the batch-decode weight-streaming GEMM, the
 ViT MFMA GEMM vs 2.5 PFLOP/s, the vision stack as a whole) and `cpu_baseline` (the CPU oracle timed on this host).
 """
@@ -70,6 +74,9 @@ def parse(argv=None):
                     "penalties, on-device sampler) instead of greedy; a side measurement, not BASELINE's metric")
     ap.add_argument("--cpu-tokens", type=int, default=32, help="decode tokens of the CPU baseline run (32 = BASELINE configs[0], timed in full)")
     ap.add_argument("--plumbing-check", action="store_true", help="CPU / gloo check of the multi-rank launch, sharding, gather and timing path (no model)")
+    ap.add_argument("--full", action="store_true", help="also run what the headline figure does not need: the stage breakdown, the other legs "
+                    "(--steps-b64 / -c4 / -strong / -strong-c4), the rooflines and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the ids the last timed step generated to DIR/tokens.npy (float64)")
     return ap.parse_args(argv)
 
 
@@ -530,9 +537,9 @@ def plumbing_check(args, rank, world):
     dt, out = timed_workload(step, args.steps, args.warmup, world, lambda: None, barrier, allmax)
     want = torch.arange(gB)[:, None] * 1000 + torch.arange(n_new)[None, :]
     assert torch.equal(out, want), (rank, out, want)
-    # the `strong256` leg of the real run: a GLOBAL batch of 256 split over the ranks (shard sizes 256 // world), gathered the same way
+    # the `strong256` leg of the real --full run: a GLOBAL batch of 256 split over the ranks (shard sizes 256 // world), gathered the same way
     strong = None
-    if args.steps_strong > 0 and 256 % world == 0:
+    if args.full and args.steps_strong > 0 and 256 % world == 0:
         slo, shi = shard_range(256, rank, world)
         assert shi - slo == 256 // world
 
@@ -576,6 +583,7 @@ def main():
         dist.init_process_group(backend="nccl", device_id=torch.device("cuda", local))
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
+    torch.manual_seed(0)        # --sample draws its uniforms from the default generators: same arguments, same outputs
 
     import visualcla
     from visualcla.distributed import gather_tokens, shard_range
@@ -600,11 +608,12 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         return float(tt.item())
 
-    def run_workload(B, steps, warmup):
+    def run_workload(B, steps, warmup, dump_dir=None):
         """B requests per GPU: every rank builds ONLY its shard of the global batch (request r is seeded by r, so a shard does
         not depend on the world size), generate() + one all-gather of the ids per step.  Two throughput definitions per leg:
         `images_per_sec` = whole requests (vision + prefill + all decode steps), `images_per_sec_prefill` = SURVEY.md 8(d)'s "images through
-        ViT + Resampler + projection + prefill" (one generate(max_new_tokens=1) per batch, timed on every rank, max over ranks)."""
+        ViT + Resampler + projection + prefill" (one generate(max_new_tokens=1) per batch, timed on every rank, max over ranks; --full only,
+        with the stage breakdown).  dump_dir: rank 0 writes the gathered ids of the last timed step there."""
         gB = B * world
         lo, hi = shard_range(gB, rank, world)
         px, ids, mask = make_inputs(model.config, hi - lo, args.prompt_len, first_request=lo)
@@ -621,6 +630,12 @@ def main():
         assert out.shape == (gB, args.new_tokens), out.shape
         res = {"batch_per_gpu": B, "global_batch": gB, "steps": steps, "ms_per_step": round(dt / steps * 1e3, 2),
                "tokens_per_sec": round(gB * args.new_tokens * steps / dt, 2), "images_per_sec": round(gB * steps / dt, 4)}
+        if dump_dir and rank == 0:
+            import numpy as np
+            os.makedirs(dump_dir, exist_ok=True)
+            np.save(os.path.join(dump_dir, "tokens.npy"), out.cpu().numpy().astype(np.float64))    # [global batch, new tokens] ids
+        if not args.full:
+            return res
 
         def timed(fn, reps=2):       # barrier + sync on both sides, max over ranks: the same bracket as the main measurement
             fn()
@@ -653,18 +668,18 @@ def main():
         if args.global_batch % world:
             raise SystemExit(f"--global-batch {args.global_batch} is not a multiple of the {world} ranks")
         args.batch = args.global_batch // world
-    main_res = run_workload(args.batch, args.steps, args.warmup)
+    main_res = run_workload(args.batch, args.steps, args.warmup, dump_dir=args.dump_outputs)
     # the roofline of the headline workload's dominant kernel is measured HERE, straight after its timed region and before the other legs run (the
     # batch-256 legs leave the device in another thermal / clock state: rounds 1 - 6a measured it last and the same kernel read 1 - 2 % slower there)
     main_rl = None
-    if rank == 0 and not args.fp8:
+    if args.full and rank == 0 and not args.fp8:
         main_rl = (engine_roofline(model, args.prompt_len) or gemv_roofline(model)) if args.batch == 1 else batch_decode_gemm_roofline(model, min(args.batch, 256))
     b64_res = None
-    if args.steps_b64 > 0 and args.batch == 1 and not strong:
+    if args.full and args.steps_b64 > 0 and args.batch == 1 and not strong:
         b64_res = run_workload(64, args.steps_b64, 1)
 
     c4_res = None
-    if args.steps_c4 > 0 and args.batch == 1 and not strong and not args.fp8 and args.image_size == 224:
+    if args.full and args.steps_c4 > 0 and args.batch == 1 and not strong and not args.fp8 and args.image_size == 224:
         # BASELINE configs[4], one GPU's share (B = 256 / 8): fp8 weight copies, 336-px patching (577 ViT tokens), timed in BOTH numeric modes:
         #   headline  W8A16: fp8 weights in the decode kernels (dequantised in registers), the prefill on the bf16 MFMA tiles -- the analogue of the
         #             reference's weight-only `load_in_8bit` (models/visualcla/modeling_visualcla.py:151-156) and what from_*_pretrained(load_in_8bit=True) selects;
@@ -686,14 +701,14 @@ def main():
         c4_res = dict(legs["w8a16"], mode="w8a16", w8a8=legs["w8a8"])
 
     strong_res = None
-    if args.steps_strong > 0 and args.batch == 1 and not strong and not args.fp8 and args.image_size == 224 and not args.sample and 256 % world == 0:
+    if args.full and args.steps_strong > 0 and args.batch == 1 and not strong and not args.fp8 and args.image_size == 224 and not args.sample and 256 % world == 0:
         # north_star: ">= 6x images/sec scaling 1 -> 8 GPUs at batch 256": the GLOBAL batch is fixed at 256 and split over the ranks (B = 256 on
-        # one GPU ... B = 32 on each of 8), so the driver's `bench.py --gpus N` series reads that curve off this leg without any flag
+        # one GPU ... B = 32 on each of 8), so a `bench.py --full --gpus N` series reads that curve off this leg
         strong_res = run_workload(256 // world, args.steps_strong, 1)
         strong_res["scaling"] = "strong"
 
     strong_c4_res = None
-    if args.steps_strong_c4 > 0 and args.batch == 1 and not strong and not args.fp8 and args.image_size == 224 and not args.sample and 256 % world == 0:
+    if args.full and args.steps_strong_c4 > 0 and args.batch == 1 and not strong and not args.fp8 and args.image_size == 224 and not args.sample and 256 % world == 0:
         # configs[4]'s own strong-scaling leg: "fp8 weight path + 336 px, batch 256 on 8 GPUs" -- the global batch of 256 split over the ranks in the SAME
         # numeric mode `config4` headlines (W8A16: fp8 weights in the decode kernels, bf16 MFMA prefill), so an 8-GPU series has its N = 1 denominator
         model.set_image_size(336)
@@ -734,55 +749,57 @@ def main():
             "value": main_res["tokens_per_sec"], "unit": "tokens/s",
             # images/sec is the throughput figure of BASELINE configs[2] (B = 64 per GPU) when that workload ran, else the main workload's
             "images_per_sec": (b64_res or main_res)["images_per_sec"],
-            "images_per_sec_prefill": (b64_res or main_res)["images_per_sec_prefill"],
             "images_per_sec_workload": (f"batch={(b64_res or main_res)['batch_per_gpu']}/GPU; images_per_sec = whole requests (vision + prefill + "
-                                        f"{args.new_tokens} decode steps), images_per_sec_prefill = images through ViT + Resampler + projection + prefill "
-                                        "(SURVEY.md 8d), one first-token generate() per batch"),
+                                        f"{args.new_tokens} decode steps)" +
+                                        (", images_per_sec_prefill = images through ViT + Resampler + projection + prefill "
+                                         "(SURVEY.md 8d), one first-token generate() per batch" if args.full else "")),
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": main_res["ms_per_step"],
             "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None,
             "dtype": "bf16" if not args.fp8 else ("fp8-e4m3 weights: W8A16 in the decode steps (dequantised in registers), W8A8 on the fp8 MFMA pipe in the "
                                                   "prefill (per-row e4m3 activations)" + ("; e4m3 K/V cache (unit scale)" if args.fp8_kv else "") +
                                                   "; bf16 activations elsewhere, fp32 accumulate"),
             "data": "synthetic (random-init 7B weights, N(0,1) pixels, synthetic ids)", "config": cfgd,
-            "breakdown_ms": main_res.get("breakdown_ms"),
         }
-        if b64_res:
-            res["config2"] = dict(b64_res, workload=workload_name(64, b64_res["global_batch"], 224, False, False, False, False))
-        if strong_res:
-            res["strong256"] = dict(strong_res, workload=f"VisualCLA-7B bf16, GLOBAL batch 256 split over {world} GPU(s) = {256 // world} image(s)/GPU, 224 px, T=128, "
-                                                          f"{args.new_tokens} greedy tokens (north_star's strong-scaling workload: compare images_per_sec / "
-                                                          "images_per_sec_prefill of this leg across --gpus 1 / 2 / 4 / 8)")
-        if strong_c4_res:
-            res["strong256_fp8_336"] = dict(strong_c4_res, workload=workload_name(256 // world, 256, 336, True, False, bool(args.fp8_kv), False, 256) +
-                                            " -- the N = 1 ... 8 series of this leg is configs[4]'s scaling curve, in the mode `config4` headlines")
-        if c4_res:
-            res["config4"] = dict(c4_res, workload="VisualCLA-7B, fp8 weight path, 336 px (577 ViT tokens), batch=32 image(s)/GPU = 256 / 8, T=128, "
-                                                   "128 greedy tokens (BASELINE configs[4], one GPU's share); headline mode w8a16, the W8A8 prefill mode under `w8a8`")
-        b1 = main_res if B == 1 else None
-        b64 = b64_res if b64_res else (main_res if B == 64 else None)
-        rl = []
-        if not args.fp8:
-            res["roofline"] = main_rl
-            rl.append(main_rl)
-            if B == 1 and b64:
-                r = batch_decode_gemm_roofline(model, 64)
+        if args.full:
+            res["images_per_sec_prefill"] = (b64_res or main_res)["images_per_sec_prefill"]
+            res["breakdown_ms"] = main_res["breakdown_ms"]
+            if b64_res:
+                res["config2"] = dict(b64_res, workload=workload_name(64, b64_res["global_batch"], 224, False, False, False, False))
+            if strong_res:
+                res["strong256"] = dict(strong_res, workload=f"VisualCLA-7B bf16, GLOBAL batch 256 split over {world} GPU(s) = {256 // world} image(s)/GPU, 224 px, T=128, "
+                                                              f"{args.new_tokens} greedy tokens (north_star's strong-scaling workload: compare images_per_sec / "
+                                                              "images_per_sec_prefill of this leg across --gpus 1 / 2 / 4 / 8)")
+            if strong_c4_res:
+                res["strong256_fp8_336"] = dict(strong_c4_res, workload=workload_name(256 // world, 256, 336, True, False, bool(args.fp8_kv), False, 256) +
+                                                " -- the N = 1 ... 8 series of this leg is configs[4]'s scaling curve, in the mode `config4` headlines")
+            if c4_res:
+                res["config4"] = dict(c4_res, workload="VisualCLA-7B, fp8 weight path, 336 px (577 ViT tokens), batch=32 image(s)/GPU = 256 / 8, T=128, "
+                                                       "128 greedy tokens (BASELINE configs[4], one GPU's share); headline mode w8a16, the W8A8 prefill mode under `w8a8`")
+            b1 = main_res if B == 1 else None
+            b64 = b64_res if b64_res else (main_res if B == 64 else None)
+            rl = []
+            if not args.fp8:
+                res["roofline"] = main_rl
+                rl.append(main_rl)
+                if B == 1 and b64:
+                    r = batch_decode_gemm_roofline(model, 64)
+                    if r:
+                        rl.append(r)
+                if args.image_size == 224:
+                    rl.append(vit_gemm_roofline(model, 64))
+            else:
+                r = fp8_gemm_roofline(model)
+                res["roofline"] = r
                 if r:
                     rl.append(r)
-            if args.image_size == 224:
-                rl.append(vit_gemm_roofline(model, 64))
-        else:
-            r = fp8_gemm_roofline(model)
-            res["roofline"] = r
-            if r:
-                rl.append(r)
-        rl += step_rooflines(b1, b64, cfgd, args.fp8, bool(args.fp8_kv), main_res if B not in (1, 64) else strong_res)
-        res["rooflines"] = rl
-        if not args.no_cpu_baseline and world == 1 and args.image_size == 224:   # the CPU baseline is reported by the N=1 run only
-            try:
-                res["cpu_baseline"] = cpu_baseline(model, args.prompt_len, args.cpu_tokens)
-            except Exception as e:  # e.g. host RAM too small for the 27 GB fp32 copy
-                res["cpu_baseline"] = {"value": None, "unit": "tokens/s", "cores": os.cpu_count(), "kind": "port",
-                                       "sample": f"failed: {type(e).__name__}: {e}"}
+            rl += step_rooflines(b1, b64, cfgd, args.fp8, bool(args.fp8_kv), main_res if B not in (1, 64) else strong_res)
+            res["rooflines"] = rl
+            if not args.no_cpu_baseline and world == 1 and args.image_size == 224:   # the CPU baseline is reported by the N=1 run only
+                try:
+                    res["cpu_baseline"] = cpu_baseline(model, args.prompt_len, args.cpu_tokens)
+                except Exception as e:  # e.g. host RAM too small for the 27 GB fp32 copy
+                    res["cpu_baseline"] = {"value": None, "unit": "tokens/s", "cores": os.cpu_count(), "kind": "port",
+                                           "sample": f"failed: {type(e).__name__}: {e}"}
         print(json.dumps(res))
     if world > 1:
         dist.barrier()

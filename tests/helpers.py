@@ -1,11 +1,21 @@
 """Shared test helpers: oracle config -> VisualCLAConfig, HIP model construction from oracle weights."""
 from __future__ import annotations
 
+import os
 from types import SimpleNamespace
 
 import torch
 
 from oracle import visualcla_oracle as O
+
+
+def report(line: str) -> None:
+    """Appends one parity figure to $OUT/parity_report.txt (default: out/ at the repository root), where the tools/*.sh scripts
+    that run the GPU suite collect it."""
+    out = os.environ.get("OUT") or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "out")
+    os.makedirs(out, exist_ok=True)
+    with open(os.path.join(out, "parity_report.txt"), "a") as f:
+        f.write(line + "\n")
 
 
 def to_vcla_config(cfg: O.OracleCfg):

@@ -55,6 +55,5 @@ def test_rccl_world1_gathers_device_int64_tokens(tmp_path):
     r = subprocess.run([sys.executable, str(script), ROOT], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "RCCL_OK" in r.stdout, (r.stdout[-2000:], r.stderr[-3000:])
     assert "librccl" in r.stdout, r.stdout          # the collective really went through RCCL's shared object
-    os.makedirs("gpurun_out", exist_ok=True)
-    with open("gpurun_out/parity_report.txt", "a") as f:
-        f.write("rccl world-1: nccl backend initialised, gather_tokens(force_collective) int64 device tensors OK; " + r.stdout.strip().splitlines()[-1] + "\n")
+    from tests.helpers import report
+    report("rccl world-1: nccl backend initialised, gather_tokens(force_collective) int64 device tensors OK; " + r.stdout.strip().splitlines()[-1])

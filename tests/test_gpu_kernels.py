@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from oracle import visualcla_oracle as O
+from tests.helpers import report as _report
 
 pytestmark = pytest.mark.gpu
 
@@ -20,12 +21,6 @@ def lib():
     from visualcla import _lib
     _lib.require_device()
     return _lib
-
-
-def _report(line: str):
-    os.makedirs("gpurun_out", exist_ok=True)
-    with open("gpurun_out/parity_report.txt", "a") as f:
-        f.write(line + "\n")
 
 
 def bf16r(t):

@@ -17,15 +17,10 @@ import torch
 
 from oracle import visualcla_oracle as O
 from tests.helpers import make_hip_model, to_vcla_config, stub_tokenizer
+from tests.helpers import report as _report
 
 pytestmark = pytest.mark.gpu
 CASES = {"tiny_b2": O.cfg_tiny, "small_b2": O.cfg_small}
-
-
-def _report(line):
-    os.makedirs("gpurun_out", exist_ok=True)
-    with open("gpurun_out/parity_report.txt", "a") as f:
-        f.write(line + "\n")
 
 
 def _setup(name, golden_dir):

@@ -181,14 +181,14 @@ def test_bench_self_spawns_ranks_and_gathers_once():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--plumbing-check"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--plumbing-check", "--full"],
                        capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stdout + r.stderr
     line = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(line) == 1, r.stdout
     res = json.loads(line[0])
     assert res["n_gpus"] == 2 and res["steps"] == 2 and res["config"]["parallelism"] == "dp2" and res["config"]["global_batch"] == 6
-    # the default line carries north_star's strong-scaling workload (global batch 256 split over the ranks) and both images/sec definitions
+    # the --full line carries north_star's strong-scaling workload (global batch 256 split over the ranks) and both images/sec definitions
     assert res["images_per_sec"] > 0 and res["images_per_sec_prefill"] > 0
     s256 = res["strong256"]
     assert s256["global_batch"] == 256 and s256["batch_per_gpu"] == 128 and s256["scaling"] == "strong"
@@ -196,6 +196,15 @@ def test_bench_self_spawns_ranks_and_gathers_once():
     # ... and configs[4]'s own strong-scaling leg (fp8 W8A16, 336 px, the same global batch of 256): its N = 1 run is the denominator of the 8-GPU claim
     c4s = res["strong256_fp8_336"]
     assert c4s["global_batch"] == 256 and c4s["batch_per_gpu"] == 128 and c4s["scaling"] == "strong" and c4s["mode"] == "w8a16"
+    # a plain run (no --full) times the main workload only: same steps, no other legs
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--plumbing-check"],
+                       capture_output=True, text=True, timeout=300, env=env)
+    assert r.returncode == 0, r.stdout + r.stderr
+    line = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(line) == 1, r.stdout
+    res = json.loads(line[0])
+    assert res["n_gpus"] == 2 and res["steps"] == 3 and res["value"] > 0
+    assert "strong256" not in res and "strong256_fp8_336" not in res
 
 
 def test_synthetic_shards_are_slices_of_the_global_batch():

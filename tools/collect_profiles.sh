@@ -1,8 +1,11 @@
 #!/bin/bash
-# copy the judged summaries of the last `tools/gpu_check.sh [full|pmc]` run from gpurun_out/ (scratch) into profiles/ (tracked)
-# usage: bash tools/collect_profiles.sh r01 run18
+# copy the judged summaries of the last `tools/gpu_check.sh [full|pmc]` run from $OUT/ (scratch) into profiles/ (tracked)
+# usage: [OUT=dir] bash tools/collect_profiles.sh r01 run18 (the same OUT as the gpu_check.sh run; default out/)
 r=${1:-r01}; tag=${2:-run}
-o=gpurun_out; p=profiles
+R=$(cd "$(dirname "$0")/.." && pwd)
+OUT=$(realpath -m "${OUT:-$R/out}")      # where tools/gpu_check.sh wrote its results (resolved as it does)
+cd "$R"
+o=$OUT; p=profiles
 mkdir -p $p
 grep '^{' $o/bench.log        | tail -1 > $p/${r}_bench_${tag}.json
 grep '^{' $o/bench_fp8.log    | tail -1 > $p/${r}_bench_fp8_${tag}.json
