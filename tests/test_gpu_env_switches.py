@@ -1,6 +1,7 @@
-"""Every VCLA_* A/B switch the product library reads selects a kernel form that was the default at some point:
-each must still produce the reference's numbers.  One child process per setting (the switches are read once per process): small
-model, bf16, forward logits within the bf16 bound of the fp32 oracle and greedy ids equal wherever the oracle's margin allows."""
+"""Every VCLA_* A/B switch the product library reads (csrc/vcla_knobs.h) selects a kernel form that was the default at
+some point: each must still produce the reference's numbers.  One child process per setting: small model, bf16, forward logits within the
+bf16 bound of the fp32 oracle and greedy ids equal wherever the oracle's margin allows.  The library reads the switches at every outermost
+call; test_switch_flip_in_process_recaptures_the_graphs checks that a flip inside one process reaches the cached graphs."""
 import json
 import os
 import subprocess
@@ -15,24 +16,14 @@ SETTINGS = [
     {},                                     # defaults
     {"VCLA_DSTREAM": "0"},                  # split-K panel kernels instead of the streaming decode GEMMs
     {"VCLA_DS_DEFER": "0"},                 # a norm launch per RMSNorm instead of the deferred form
-    {"VCLA_DS_SPLITK": "2"},
-    {"VCLA_DS_GRID": "128"},
     {"VCLA_DS_QKV_SPLIT": "0"},             # qkv unsplit + plain decode attention instead of two raw K slices summed by the attention kernel
     {"VCLA_GEMV1X": "0"},                   # runtime-K decode GEMV
-    {"VCLA_GEMV_OCC": "1"},
-    {"VCLA_ATTN_FLASH": "0"},               # the phased decode attention of round 2
-    {"VCLA_ATTN_FLASH": "0", "VCLA_ATTN_NW": "4", "VCLA_ATTN_COOP": "1"},
     {"VCLA_ATTN_MFMA_WHOLE": "0"},
-    {"VCLA_ATTN_MFMA_NW": "4"},
-    {"VCLA_GEMM_PERSIST": "1"},
     {"VCLA_GEMM_PF": "0"},                  # the 256 x 256 GEMM without the L2 prefetch (and without 257-row tiles)
     {"VCLA_GEMM_XR": "0"},                  # 256-row tiles + a tail launch for the ViT's M = B * 257
     {"VCLA_MFMA128_SPLITK": "0"},
-    {"VCLA_TAIL_KERNEL": "7"},
-    {"VCLA_TAIL_KERNEL": "8"},
     {"VCLA_MACRO_GRAPH": "0"},
     {"VCLA_DECODE_GRAPH": "0"},
-    {"VCLA_GRAPH_STEPS": "2"},
 ]
 
 
@@ -86,6 +77,52 @@ def test_macro_graphs_keep_two_shapes_cached(tmp_path):
         lines = [ln for ln in chunk.splitlines() if "macro graph" in ln]
         if i >= 4:
             assert lines and all("replay" in ln for ln in lines), (i, lines)
+
+
+FLIP_CHILD = r"""
+import os, sys, torch
+ROOT = sys.argv[1]
+for p in (ROOT, os.path.join(ROOT, "visual-chinese-llama-alpaca_amd")):
+    sys.path.insert(0, p)
+from oracle import visualcla_oracle as O
+from tests.helpers import cfg_engine_small, make_hip_model
+cfg = cfg_engine_small()
+W = O.make_weights(cfg, seed=1)
+m = make_hip_model(cfg, W, torch.bfloat16)
+assert "llama.engine.w" in m._packed
+px, ids, mask = (t.cuda() if i else t.cuda().to(torch.bfloat16) for i, t in enumerate(O.make_inputs(cfg, 1, 24)))   # resident request buffers
+toks = []
+for i in range(3):
+    if i == 2:       # same forms at this geometry (contexts < 512, no ring-tile ViT shape), other switch values: the cached graphs must not be replayed
+        os.environ["VCLA_ENGINE_SPLIT"] = "0"
+        os.environ["VCLA_RING_VIT"] = "0"
+    print(f"CALL {i}", file=sys.stderr, flush=True)
+    toks.append(m.generate(input_ids=ids, pixel_values=px, attention_mask=mask, max_new_tokens=6, do_sample=False, eos_token_id=None).cpu())
+    torch.cuda.synchronize()
+assert all(torch.equal(t, toks[0]) for t in toks), [t.tolist() for t in toks]
+print("FLIP_OK")
+"""
+
+
+def test_switch_flip_in_process_recaptures_the_graphs(tmp_path):
+    """the switches are read at every outermost call and the snapshot is part of every graph key: generate() twice (B = 1, the persistent decode
+    step; the second call replays the vision, prefill and decode graphs), then VCLA_ENGINE_SPLIT and VCLA_RING_VIT change inside the process --
+    the next call runs the macro graphs eagerly on a new key and captures the decode graph again instead of replaying graphs chosen under the old
+    values; the tokens stay the same"""
+    script = tmp_path / "flip_child.py"
+    script.write_text(FLIP_CHILD)
+    env = {k: v for k, v in os.environ.items() if not k.startswith("VCLA_") or k == "VCLA_LIB"}
+    env["VCLA_MACRO_GRAPH_DEBUG"] = "1"
+    r = subprocess.run([sys.executable, str(script), ROOT], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and "FLIP_OK" in r.stdout, r.stderr[-3000:]
+    calls = r.stderr.split("CALL ")[1:]
+    assert len(calls) == 3, r.stderr[-3000:]
+    macro = [[ln for ln in c.splitlines() if "macro graph" in ln] for c in calls]
+    decode = [[ln for ln in c.splitlines() if "decode graph" in ln] for c in calls]
+    assert macro[1] and all("replay" in ln for ln in macro[1]), macro[1]
+    assert decode[1] and all("replay" in ln for ln in decode[1]), decode[1]
+    assert macro[2] and not any("replay" in ln for ln in macro[2]), macro[2]
+    assert decode[2] and any("capture" in ln for ln in decode[2]) and not any("replay" in ln for ln in decode[2]), decode[2]
 
 
 VIT_CHILD = r"""

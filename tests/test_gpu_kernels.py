@@ -1027,7 +1027,9 @@ def test_panel_splitk_handoff_stress(lib):
     _report(f"panel split-K stress: worst |err| {worst:.3e} over 40 x {len(cases)} launches")
 
 
-@pytest.mark.parametrize("M,N,K,epi", [(4 * 257, 1024, 1024, 0), (8 * 257, 4096, 1024, 1), (1100, 512, 256, 0), (2 * 256 + 128, 768, 128, 2)])
+@pytest.mark.parametrize("M,N,K,epi", [(4 * 257, 1024, 1024, 0), (8 * 257, 4096, 1024, 1), (1100, 512, 256, 0), (2 * 256 + 128, 768, 128, 2),
+                                       # 256 whole 256 x 256 tiles + a 64-row tail: the skinny kernel (K <= 2048) / the split-K panel kernel (longer K)
+                                       (4096 + 64, 4096, 1024, 0), (4096 + 64, 4096, 2304, 1)])
 def test_gemm_auto_dispatch_ragged_m(lib, M, N, K, epi):
     """auto dispatch peels the M % 256 tail of ragged problems (ViT rows = B*257) into a second launch: results must be
     seamless across the split, including bias / activation / in-place residual"""

@@ -424,7 +424,7 @@ def main():
                   f" = {(tot['k9'] + 2 * tp)*1e6:.1f} us ({404e6/(tot['k9'] + 2 * tp)/1e9:.0f} GB/s over 404 MB) || fp8: k8 {tot['k8q']*1e6:.1f} | k9 {tot['k9q']*1e6:.1f} us")
     if "dec256" in which:
         # decode batches of 65 - 256 rows: the row-major MFMA tile kernels through the product dispatch (what engine.hip's llama_layer
-        # issues), rotating over 4 weight buffers.  VCLA_MFMA128_S forces the K-slice count of the 128-tile kernel, VCLA_BENCH_FK the kernel.
+        # issues), rotating over 4 weight buffers.  VCLA_BENCH_FK forces the kernel.
         print("== decode GEMMs at 65 <= M <= 256 (product dispatch); env: " + " ".join(f"{k}={v}" for k, v in os.environ.items() if k.startswith("VCLA_")))
         skws = torch.zeros(64 << 20, dtype=torch.uint8, device=DEV)
         fk = int(os.environ.get("VCLA_BENCH_FK", "0"))
@@ -471,7 +471,7 @@ def main():
             print(f"{tag:24s} M={M:6d} N={N:6d} K={K:6d}  k4 {t4*1e6:8.1f} us {fl/t4/1e12:7.1f} TF/s ({fl/t4/2.5e13:.1f}%) | k10 {t10*1e6:8.1f} us {fl/t10/1e12:7.1f} TF/s "
                   f"({fl/t10/5e13:.1f}% of 5 PF) | quantise A {tq*1e6:6.1f} us")
     if "panel" in which:
-        print(f"== panel split-K kernel (fragment-major W), M=64, env: " + " ".join(f"{k}={v}" for k, v in os.environ.items() if k.startswith("VCLA_PANEL")))
+        print("== panel split-K kernel (fragment-major W), M=64")
         skws = torch.zeros(64 << 20, dtype=torch.uint8, device=DEV)
         from visualcla.weights import to_fragment_major
         tot = tot8 = 0.0

@@ -4,14 +4,8 @@
 done / epilogue issued / stores drained) and prints the phase durations averaged over the workgroups, per dispatch round."""
 import ctypes as C, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-ABL = {0: "full kernel", 1: "no fragment reads (MFMA + DMA)", 2: "no MFMAs (LDS reads + DMA)", 3: "no DMA after the first slab (MFMA + LDS reads)"}
-if len(sys.argv) < 2:      # one child process per build: the library is chosen at import (VCLA_LIB)
-    for abl in (0, 1, 2, 3):
-        lib = os.path.join(ROOT, "tools", "libvcla_timeline.so" if abl == 0 else f"libvcla_timeline_abl{abl}.so")
-        if os.path.exists(lib):
-            subprocess.call([sys.executable, os.path.abspath(__file__), str(abl)], env=dict(os.environ, VCLA_LIB=lib))
-    sys.exit(0)
-abl = int(sys.argv[1])
+if "VCLA_LIB" not in os.environ:      # a child process on the timeline build: the library is chosen at import (VCLA_LIB)
+    sys.exit(subprocess.call([sys.executable, os.path.abspath(__file__)], env=dict(os.environ, VCLA_LIB=os.path.join(ROOT, "tools", "libvcla_timeline.so"))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "visual-chinese-llama-alpaca_amd"))
 import torch
 from visualcla import _lib
@@ -21,7 +15,7 @@ DEV = "cuda:0"
 def rnd(*s, scale=1.0): return (torch.randn(*s, device=DEV) * scale).to(torch.bfloat16)
 def packw(n, k):
     w = torch.zeros((n + 127) // 128 * 128, k, dtype=torch.bfloat16, device=DEV); w[:n] = rnd(n, k, scale=0.02); return w
-print(f"==== {ABL[abl]}; VCLA_GEMM_PF={os.environ.get('VCLA_GEMM_PF', '1 (default)')}")
+print(f"==== VCLA_GEMM_PF={os.environ.get('VCLA_GEMM_PF', '1 (default)')}")
 for tag, M, N, K, epi in (("vit qkv", 16384, 3072, 1024, 0), ("vit fc1", 16384, 4096, 1024, 1), ("vit fc2", 16384, 1024, 4096, 0),
                           ("vit fc1, 257-row tiles", 16448, 4096, 1024, 1), ("llama qkv prefill", 8192, 12288, 4096, 0)):
     a, w = rnd(M, K), packw(N, K)

@@ -152,6 +152,7 @@ static int launch_generic(const vcla_attn_args* a, hipStream_t s) {
 }
 
 extern "C" int vcla_attention(const vcla_attn_args* a, int dtype, void* stream) {
+    VCLA_KNOBS_SCOPE();
     VCLA_REQUIRE(a, VCLA_ERR_BAD_ARG, "attention: null args");
     VCLA_REQUIRE(dtype == VCLA_F32 || dtype == VCLA_BF16, VCLA_ERR_BAD_DTYPE, "attention: bad dtype %d", dtype);
     VCLA_REQUIRE(a->D == 32 || a->D == 64 || a->D == 128, VCLA_ERR_BAD_SHAPE, "attention: head dim %d not in {32,64,128}", a->D);

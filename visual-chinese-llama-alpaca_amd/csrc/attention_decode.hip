@@ -607,19 +607,17 @@ static int launch_decode(const void* qkv, void* kc, void* vc, const float* cos_t
     const int sc_cap = (ctx_max + 63) & ~63;
     // batch form: 2-wave workgroups (8 per CU: one round for B * H <= 2048) while the context is short enough that the extra
     // passes over K and V (64 instead of 128 rows per pass) cost less than the second round of workgroups saves
-    // (measured at B = 64, H = 32, context 192: 46.0 -> 42.4 us per launch; VCLA_ATTN_NW=4 restores the 4-wave form)
-    static const int nw_env = getenv("VCLA_ATTN_NW") ? atoi(getenv("VCLA_ATTN_NW")) : 0;
-    const int NWs = (D == 128 && (int64_t)B * H >= 1024 && nw_env != 4) ? 2 : 4;
+    // (measured at B = 64, H = 32, context 192: 46.0 -> 42.4 us per launch against the 4-wave form)
+    const int NWs = (D == 128 && (int64_t)B * H >= 1024) ? 2 : 4;
     const size_t lds = (size_t)(3 * D + 2 * NWs + NWs * D + sc_cap) * sizeof(float);
     VCLA_REQUIRE(lds <= 64 * 1024, VCLA_ERR_BAD_SHAPE, "attn_decode: ctx_max=%d needs %zu B of LDS (max 64 KiB)", ctx_max, lds);
     dim3 grid(H, B);
     const int out_frag_mt = out_frag ? (B + 15) / 16 : 0;
     if constexpr (sizeof(T) == 2) {
-        // bf16: the single-pass kernel (VCLA_ATTN_FLASH=0 restores the phased kernel below for A/B runs).  2-wave workgroups once
+        // bf16: the single-pass kernel (the phased kernel below serves fp32 and the outputs it cannot store).  2-wave workgroups once
         // B * H fills the chip that way (16 per CU by waves), 4 waves otherwise; the row-major output needs 16-byte rows.
-        static const int flash_env = getenv("VCLA_ATTN_FLASH") ? atoi(getenv("VCLA_ATTN_FLASH")) : 1;
         const bool flash_ok = out_frag || (((int64_t)H * D) % 8 == 0 && vcla_aligned(out, 16));
-        const bool small_wg = (int64_t)B * H >= 1024 && nw_env != 4;
+        const bool small_wg = (int64_t)B * H >= 1024;
 #define FD_GO(NW_, MASK_, KV8_) attn_decode_flash_kernel<D, NW_, MASK_, KV8_><<<grid, NW_ * 64, 0, s>>>(qkv, kc, vc, cos_tab, sin_tab, \
                                                     (bf16_t*)out, H, ctx_max, pos0, pos_dev, key_mask, key_mask_ld, scale, out_frag_mt)
         if (qp) {    // q / k / v arrive as two raw fp32 K slices of the qkv projection: 2-wave form only (batch decode, B * H >= 1024)
@@ -647,7 +645,7 @@ static int launch_decode(const void* qkv, void* kc, void* vc, const float* cos_t
                 return vcla_fail(VCLA_ERR_BAD_SHAPE, "attn_decode: the fp8 cache needs head dim 64 or 128 (got %d)", D);
             }
         }
-        if (flash_env && flash_ok) {
+        if (flash_ok) {
             if (small_wg) { if (key_mask) FD_GO(2, true, false); else FD_GO(2, false, false); }
             else { if (key_mask) FD_GO(4, true, false); else FD_GO(4, false, false); }
             VCLA_CHECK_LAUNCH("attn_decode_flash_kernel");
@@ -655,8 +653,7 @@ static int launch_decode(const void* qkv, void* kc, void* vc, const float* cos_t
         }
 #undef FD_GO
     }
-    static const int coop_env = getenv("VCLA_ATTN_COOP") ? atoi(getenv("VCLA_ATTN_COOP")) : -1;   // -1 auto, 0 / 1 force (A/B runs)
-    const bool coop = coop_env >= 0 ? coop_env != 0 : (int64_t)B * H >= 512;
+    const bool coop = (int64_t)B * H >= 512;
     if (coop && NWs == 2)
         attn_decode_kernel<T, D, true, 2><<<grid, 128, lds, s>>>((const T*)qkv, (T*)kc, (T*)vc, cos_tab, sin_tab, (T*)out, H, ctx_max, pos0,
                                                                  pos_dev, key_mask, key_mask_ld, scale, sc_cap, out_frag_mt);
@@ -678,6 +675,7 @@ extern "C" int vcla_attn_decode_fused_parts(const float* qkv_parts, int64_t slic
                                             void* k_cache, void* v_cache, const float* cos_tab, const float* sin_tab, void* out, int B, int H, int d,
                                             int ctx_max, int pos0, const int32_t* pos_dev, const int32_t* key_mask, int64_t key_mask_ld, float scale,
                                             int dtype, int out_frag, void* stream) {
+    VCLA_KNOBS_SCOPE();
     VCLA_REQUIRE(qkv_parts && slice_stride >= (int64_t)B * 3 * H * d && vcla_aligned(qkv_parts, 16), VCLA_ERR_BAD_ARG,
                  "attn_decode_parts: qkv_parts = two fp32 slices [B][3 H d], slice_stride elements apart");
     VCLA_REQUIRE((dtype & ~VCLA_KV_FP8) == VCLA_BF16, VCLA_ERR_BAD_DTYPE, "attn_decode_parts: bf16 activations only");
@@ -690,6 +688,7 @@ extern "C" int vcla_attn_decode_fused(const void* qkv, void* k_cache, void* v_ca
                                       const float* sin_tab, void* out, int B, int H, int d, int ctx_max, int pos0,
                                       const int32_t* pos_dev, const int32_t* key_mask, int64_t key_mask_ld, float scale,
                                       int dtype, int out_frag, void* stream) {
+    VCLA_KNOBS_SCOPE();
     return attn_decode_entry(qkv, k_cache, v_cache, cos_tab, sin_tab, out, B, H, d, ctx_max, pos0, pos_dev, key_mask, key_mask_ld, scale, dtype, out_frag, stream,
                              nullptr);
 }

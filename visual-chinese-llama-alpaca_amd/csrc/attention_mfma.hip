@@ -349,9 +349,7 @@ __global__ __launch_bounds__(NW * 64) void attn_mfma_kernel(vcla_attn_args a) {
 //     (max, sum, sum p v[d = lane]) and parks them in LDS; wave 0 merges the NWM partials at the end.  No wave is spent on one row.
 // 4 waves x ~200 registers: two workgroups per CU (LDS 2 x 66 KiB), 8 waves -- the second workgroup's MFMAs run under the first
 // one's softmax.
-// ABL != 0: timing ablations for tools/bench_kernels.py (VCLA_ATTN_VIT_ABL; results are garbage): 1 = no last-row VALU phase, 2 = no v_exp
-// in the softmax, 3 = no key-tile loop at all (staging + epilogue only), 4 = tile loop without the softmax VALU work.
-template <int NWM, int ABL = 0>
+template <int NWM>
 __global__ __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(2, 2))) void attn_vit_kernel(vcla_attn_args a) {
     constexpr int D = 64, KST = 2, DT = 4, CH = 8, QT = 4, NT = NWM * 64, NK = NWM * 64 + 1;
     constexpr int KV_BYTES = NK * D * 2;                              // one operand image: [NK keys][128 B], chunk-swizzled
@@ -402,7 +400,7 @@ __global__ __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(2, 2))
     __syncthreads();
 
     // ---- last query row against this wave's 64 keys (wave 0: + the last key), on the VALU
-    if constexpr (ABL != 1) {
+    {
         auto qdot = [&](int key) {
             float d_ = 0.f;
 #pragma unroll
@@ -443,7 +441,7 @@ __global__ __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(2, 2))
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) { m_run[qt] = -INFINITY; l_run[qt] = 0.f; }
 
-    for (int tile = 0; tile < (ABL == 3 ? 0 : NWM); ++tile) {
+    for (int tile = 0; tile < NWM; ++tile) {
         const unsigned char* ks = ks_all + tile * (64 * D * 2);
         const auto vbase = (__attribute__((address_space(3))) unsigned char*)lds_all + KV_BYTES + tile * (64 * D * 2);
         f32x4_t sacc[QT][4];
@@ -479,18 +477,13 @@ __global__ __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(2, 2))
             for (int t = 0; t < 4; ++t)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    float p;
-                    if constexpr (ABL == 2) p = __builtin_fmaf(sacc[qt][t][r], sl2, -m_new);
-                    else if constexpr (ABL == 4) p = sacc[qt][t][r];
-                    else p = __builtin_amdgcn_exp2f(__builtin_fmaf(sacc[qt][t][r], sl2, -m_new));
+                    const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(sacc[qt][t][r], sl2, -m_new));
                     pv[t * 4 + r] = p;
-                    if constexpr (ABL != 4) ps += p;
+                    ps += p;
                 }
             l_run[qt] = l_run[qt] * alpha + ps;
-            if constexpr (ABL != 4) {
 #pragma unroll
-                for (int dt = 0; dt < DT; ++dt) o[qt][dt] *= alpha;
-            }
+            for (int dt = 0; dt < DT; ++dt) o[qt][dt] *= alpha;
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
                 uint4 u;
@@ -579,7 +572,7 @@ __global__ __launch_bounds__(NWM * 64) __attribute__((amdgpu_waves_per_eu(2, 2))
 
 // ---- the same kernel with direct-to-LDS staging, pipelined against the key tiles (NWM = 4 only).
 // The register-staged form above is lock-stepped: both co-resident workgroups of a CU request their 96 KiB at launch, wait ~25 us for them
-// (135 MB per launch through L2: the staging + epilogue alone measure 33 of the 48 us, VCLA_ATTN_VIT_ABL=3), then compute.  Here every byte
+// (135 MB per launch through L2: the staging + epilogue alone measure 33 of the 48 us in a timing ablation without the key tiles), then compute.  Here every byte
 // moves with global_load_lds_dwordx4 issued from inline asm (no staging registers, hipcc neither counts nor drains them) in the order
 // the tile loop consumes them, and vmcnt is counted by hand: tile t is computed once the wave's own pieces of tile t have landed and the
 // workgroup has met at a bare s_barrier, while the later tiles are still in flight.  LDS images are lane-linear per DMA instruction, so the
@@ -1230,22 +1223,17 @@ int vcla_attention_vit(const vcla_attn_args* a, void* stream) {
         VCLA_CHECK_LAUNCH("attn_vit_long_kernel");
         return VCLA_OK;
     }
-    static const int abl_env = getenv("VCLA_ATTN_VIT_ABL") ? atoi(getenv("VCLA_ATTN_VIT_ABL")) : 0;
 #define VIT_GO(NWM_)                                                                                                 \
     {                                                                                                                \
         auto kern = attn_vit_kernel<NWM_>;                                                                           \
-        if ((NWM_) == 4 && abl_env == 1) kern = attn_vit_kernel<4, 1>;                                              \
-        if ((NWM_) == 4 && abl_env == 2) kern = attn_vit_kernel<4, 2>;                                              \
-        if ((NWM_) == 4 && abl_env == 3) kern = attn_vit_kernel<4, 3>;                                              \
-        if ((NWM_) == 4 && abl_env == 4) kern = attn_vit_kernel<4, 4>;                                              \
         const size_t lds = (size_t)2 * ((NWM_) * 64 + 1) * 128 + (size_t)(NWM_) * 66 * 4;                             \
         static bool attr_set[VCLA_MAX_DEVICES] = {};                                                                 \
         if (lds > 64 * 1024) { const int rc_ = vcla_raise_dyn_lds((const void*)kern, lds, attr_set); if (rc_) return rc_; } \
         kern<<<grid, (NWM_) * 64, lds, s>>>(*a);                                                                     \
     }
-    static const int vit_form = getenv("VCLA_ATTN_VIT") ? atoi(getenv("VCLA_ATTN_VIT")) : 2;   // 1 = register-staged form, 2 = direct-to-LDS pipelined form (257 tokens)
+    const int vit_form = vcla_knobs_get().attn_vit;   // 1 = register-staged form, 2 = direct-to-LDS pipelined form (257 tokens)
     const bool o16 = vcla_aligned(a->o, 16) && a->o_bs % 8 == 0 && a->o_hs % 8 == 0 && a->o_rs % 8 == 0;     // the DMA form stores O in 16-byte pieces
-    if (a->Tq == 257 && vit_form != 1 && abl_env == 0 && o16) {
+    if (a->Tq == 257 && vit_form != 1 && o16) {
         auto kern = attn_vit_dma_kernel;
         const size_t lds = (size_t)2 * 264 * 128 + 1024 + 4 * 68 * 4;
         static bool attr_set[VCLA_MAX_DEVICES] = {};
@@ -1274,22 +1262,20 @@ bool vcla_attention_mfma_supported(const vcla_attn_args* a) {
 
 int vcla_attention_mfma(const vcla_attn_args* a, void* stream) {
     hipStream_t s = (hipStream_t)stream;
-    static const int nw_env = getenv("VCLA_ATTN_MFMA_NW") ? atoi(getenv("VCLA_ATTN_MFMA_NW")) : 0;   // A/B runs: force 4
     // ViT self-attention (65 / 257 / 577 tokens, d = 64) with at least half a round of workgroups: the whole-sequence kernels
-    static const int vit_env = getenv("VCLA_ATTN_VIT") ? atoi(getenv("VCLA_ATTN_VIT")) : 1;           // A/B runs: 0 = the tile-by-tile kernel
-    if (vit_env && a->force_kernel != 2 && attn_vit_shape(a) && (int64_t)a->B * a->H >= 128) return vcla_attention_vit(a, stream);
+    // (VCLA_ATTN_VIT=0: the tile-by-tile kernel below)
+    if (vcla_knobs_get().attn_vit && a->force_kernel != 2 && attn_vit_shape(a) && (int64_t)a->B * a->H >= 128) return vcla_attention_vit(a, stream);
     // waves per workgroup: bidirectional sequences longer than one 128-row block go 288 rows at a time (ViT-L/14 224 px: the
     // whole sequence), 64-query cross attention (resampler) needs only 2 waves
     int nw = 4;
     // (the 9-wave form needs B * H >= one workgroup per CU to pay: a single image is 16 heads = 16 workgroups, 48 with 4 waves)
     if (!a->causal && a->D == 64) nw = a->Tq <= 64 ? 2 : ((a->Tq > 128 && (int64_t)a->B * a->H >= 256) ? 9 : 4);
-    if (nw_env == 4) nw = 4;
     dim3 grid((a->Tq + nw * 32 - 1) / (nw * 32), a->H, a->B);
     // key tiles the tile loop will walk (the kernel peels 1 - 4 remainder keys of an unmasked bidirectional sequence)
     int kv = a->Tk;
     if (!a->causal && !a->key_mask && a->Tk > FA_KV && a->Tk % FA_KV >= 1 && a->Tk % FA_KV <= 4) kv -= a->Tk % FA_KV;
     const int ntiles = (kv + FA_KV - 1) / FA_KV;
-    static const int whole_env = getenv("VCLA_ATTN_MFMA_WHOLE") ? atoi(getenv("VCLA_ATTN_MFMA_WHOLE")) : 1;   // A/B runs: 0 = always tile by tile
+    const int whole_env = vcla_knobs_get().attn_mfma_whole;   // A/B runs: 0 = always tile by tile
 #define FA_GO(D_, NW_, MAXT_)                                                                                        \
     {                                                                                                                \
         auto kern = attn_mfma_kernel<D_, NW_, MAXT_>;                                                                \

@@ -134,6 +134,7 @@ struct vcla_ctx {
     const void* eng_w = nullptr;
     const float* eng_g = nullptr;
     vcla_engine_geom eng_geom = {};
+    int n_cu = 0;   // CUs of the device the context was finalized on (the engine's row ownership is laid out for EG_NCU)
     int k_pad = 0;  // padded im2col width
     // per-call state of the macro entry points (one thread drives a context at a time): the workspace carve of the
     // running call and what the last streaming GEMM left behind.  Kept here, not in thread-local globals, so that nothing
@@ -146,25 +147,29 @@ struct vcla_ctx {
         int ssq_parts = 0;             // layout of the deferred-RMSNorm row statistics the last producer wrote (see gemm_ds)
     } run;
     // cached graphs of the vision stack and of the prefill (fixed launch sequences per shape: ~250 / ~290 launches that are host-bound
-    // at B = 1).  Keyed on every pointer and shape the captured launches bake in; see run_macro.
+    // at B = 1).  Keyed on every pointer and shape the captured launches bake in and on the switch snapshot that chose them; see run_macro.
     struct MacroGraph {
         static constexpr int kSlots = 2;        // two shapes in rotation (e.g. forward(all_logits) and generate()'s prefill, or two batch sizes) both stay cached
+        struct Key {
+            const void* p[8];
+            vcla_knobs knobs;
+        };
         hipGraphExec_t exec[kSlots] = {};
-        const void* key[kSlots][8] = {};        // of the captured graphs
+        Key key[kSlots] = {};                   // of the captured graphs
         unsigned long long used[kSlots] = {};   // last-use tick: the older slot is the one replaced
         unsigned long long tick = 0;
-        const void* seen[8] = {};               // of the previous eager call
+        Key seen = {};                          // of the previous eager call
         int has_seen = 0;
     } vision_graph, prefill_graph;
-    // cached decode graph
-    hipGraphExec_t graph_exec = nullptr;        // one decode step
-    hipGraphExec_t graph_exec_multi = nullptr;  // VCLA_GRAPH_STEPS decode steps (same key), built on the first loop long enough to use it
+    // cached decode graph: one decode step
+    hipGraphExec_t graph_exec = nullptr;
     struct {
         const void *ids, *kv, *mask, *ws, *out;
         int B, pos0, ctx_max, step_base;
         const void* pos_dev;
-        int has_samp, n_hist0, engine;
+        int has_samp, n_hist0;
         vcla_sample_args samp;
+        vcla_knobs knobs;
     } graph_key = {};
 };
 
@@ -210,12 +215,11 @@ extern "C" int vcla_ctx_create(const vcla_model_cfg* cfg, vcla_ctx** out) {
 static void drop_graphs(vcla_ctx* ctx) {
     // An exec may still be executing (its last hipGraphLaunch is asynchronous) and HIP does not promise deferred destruction on every ROCm
     // version: drain the device first.  Only when there is something to destroy -- registering the tensors of a fresh context costs nothing.
-    bool any = ctx->graph_exec || ctx->graph_exec_multi;
+    bool any = ctx->graph_exec != nullptr;
     for (const vcla_ctx::MacroGraph* g : {&ctx->vision_graph, &ctx->prefill_graph})
         for (int i = 0; i < vcla_ctx::MacroGraph::kSlots; ++i) any = any || g->exec[i];
     if (any && hipDeviceSynchronize() != hipSuccess) (void)hipGetLastError();
     if (ctx->graph_exec) { (void)hipGraphExecDestroy(ctx->graph_exec); ctx->graph_exec = nullptr; }
-    if (ctx->graph_exec_multi) { (void)hipGraphExecDestroy(ctx->graph_exec_multi); ctx->graph_exec_multi = nullptr; }
     for (vcla_ctx::MacroGraph* g : {&ctx->vision_graph, &ctx->prefill_graph}) {
         for (int i = 0; i < vcla_ctx::MacroGraph::kSlots; ++i)
             if (g->exec[i]) { (void)hipGraphExecDestroy(g->exec[i]); g->exec[i] = nullptr; }
@@ -368,16 +372,18 @@ extern "C" int vcla_ctx_finalize(vcla_ctx* ctx) {
     GET_F(ctx->rope_cos, "llama.rope_cos", (size_t)c.t_max_pos * (d / 2));
     GET_F(ctx->rope_sin, "llama.rope_sin", (size_t)c.t_max_pos * (d / 2));
     ctx->eng_w = nullptr; ctx->eng_g = nullptr;
+    {
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ctx->n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) {
+            (void)hipGetLastError();
+            ctx->n_cu = 0;
+        }
+    }
     if (c.act_dtype == VCLA_BF16 && !c.t_kv_fp8 && vcla_engine_geometry(c.t_hidden, c.t_heads, c.t_inter, c.t_vocab, c.t_layers, &ctx->eng_geom)) {
         const void *ew = nullptr, *eg = nullptr;
         int rc = get_tensor_opt(ctx, "llama.engine.w", (size_t)EG_NCU * ctx->eng_geom.slots_total * EG_SLOT, &ew);
         if (!rc) rc = get_tensor_opt(ctx, "llama.engine.g", (size_t)(2 * c.t_layers + 1) * EG_D * 4, &eg);
         if (rc) return rc;
-        if (!rc && !ew) {      // A/B only: "llama.engine.w.cu" = the first form of the round, [CU][slot][16 KiB] (every CU's run contiguous)
-            rc = get_tensor_opt(ctx, "llama.engine.w.cu", (size_t)EG_NCU * ctx->eng_geom.slots_total * EG_SLOT, &ew);
-            if (rc) return rc;
-            if (ew) { ctx->eng_geom.cu_stride = (size_t)ctx->eng_geom.slots_total * EG_SLOT; ctx->eng_geom.slot_stride = EG_SLOT; }
-        }
         if (ew && eg) { ctx->eng_w = ew; ctx->eng_g = (const float*)eg; }
     }
     ctx->finalized = true;
@@ -496,8 +502,7 @@ static int gemm(vcla_ctx* ctx, hipStream_t s, const void* A, int64_t lda, const 
         a.A = nullptr; a.A_q8 = ctx->run.q8_ws; a.a_scale = ctx->run.q8s_ws; a.W_q8 = wv->q8; a.w_scale = wv->s8; a.force_kernel = 10;
         return vcla_gemm(&a, ctx->c.act_dtype, s);
     }
-    static const int ring_env = getenv("VCLA_RING") ? atoi(getenv("VCLA_RING")) : 1;      // VCLA_RING=0: the round-4 dispatch everywhere (gemm.hip), also for the fp8 rows below
-    if (ring_env && wv && M > 128 && M <= 256 && ctx->run.decode_step && wv->q8 && wv->s8 && ctx->c.act_dtype == VCLA_BF16 && !norm_gamma && grp_rows == 0 &&
+    if (vcla_knobs_get().ring && wv && M > 128 && M <= 256 && ctx->run.decode_step && wv->q8 && wv->s8 && ctx->c.act_dtype == VCLA_BF16 && !norm_gamma && grp_rows == 0 &&
         (epi == VCLA_EPI_NONE || (epi == VCLA_EPI_SWIGLU && !out_f32))) {
         // BASELINE configs[4], decode batches of 129 - 256 sequences (its N = 1 leg, B = 256): the ring kernel stages the fp8 rows as they are and
         // widens them in registers -- the SAME W8A16 function of the dequantised weights the M <= 128 decode kernels compute, whatever the batch
@@ -556,18 +561,22 @@ static int tap_copy(void* tap, size_t index, const void* src, size_t bytes, hipS
 // run(stream) issues the launch sequence.  Replay when `key` matches the captured graph; capture when it matches the previous eager
 // call; else run eagerly and remember the key.  Capture is illegal on the legacy default stream (s == 0): eager there.
 template <typename F>
-static int run_macro(vcla_ctx::MacroGraph& g, const void* const (&key)[8], hipStream_t s, F&& run) {
-    static const int genv = getenv("VCLA_MACRO_GRAPH") ? atoi(getenv("VCLA_MACRO_GRAPH")) : 1;
-    if (!genv || s == nullptr) return run(s);
+static int run_macro(vcla_ctx::MacroGraph& g, const void* const (&ptrs)[8], hipStream_t s, F&& run) {
+    const vcla_knobs& kn = vcla_knobs_get();
+    if (!kn.macro_graph || s == nullptr) return run(s);
     // The caller is capturing on this stream itself (torch.cuda.graph, or its own hipGraph around this entry point): the launches
     // belong in ITS graph -- replaying ours or opening a nested capture would both be wrong.
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(s, &cap) != hipSuccess) { (void)hipGetLastError(); return run(s); }
     if (cap != hipStreamCaptureStatusNone) return run(s);
-    static const int dbg = getenv("VCLA_MACRO_GRAPH_DEBUG") ? atoi(getenv("VCLA_MACRO_GRAPH_DEBUG")) : 0;
+    const int dbg = kn.macro_graph_debug;
+    vcla_ctx::MacroGraph::Key key;
+    memset(&key, 0, sizeof key);
+    memcpy(key.p, ptrs, sizeof key.p);
+    key.knobs = kn;
     constexpr int NS = vcla_ctx::MacroGraph::kSlots;
     for (int i = 0; i < NS; ++i) {
-        if (g.exec[i] && memcmp(g.key[i], key, sizeof(g.key[i])) == 0) {
+        if (g.exec[i] && memcmp(&g.key[i], &key, sizeof key) == 0) {
             VCLA_CHECK_HIP(hipGraphLaunch(g.exec[i], s));
             g.used[i] = ++g.tick;
             if (dbg) fprintf(stderr, "[vcla] macro graph %p: replay (slot %d)\n", (void*)&g, i);
@@ -578,9 +587,9 @@ static int run_macro(vcla_ctx::MacroGraph& g, const void* const (&key)[8], hipSt
     // not a captured key: this call runs eagerly (which also leaves every per-device function attribute set); the graph is
     // captured behind it -- recorded, not executed -- when the key is the very first one or repeats the previous eager call's, so a
     // caller whose buffers move on every call never pays for captures it cannot reuse
-    const bool repeat = g.has_seen && memcmp(g.seen, key, sizeof(g.seen)) == 0;
+    const bool repeat = g.has_seen && memcmp(&g.seen, &key, sizeof key) == 0;
     const bool first = !g.has_seen;
-    memcpy(g.seen, key, sizeof(g.seen));
+    g.seen = key;
     g.has_seen = 1;
     const int rc_eager = run(s);
     if (rc_eager || !(repeat || first)) return rc_eager;
@@ -612,7 +621,7 @@ static int run_macro(vcla_ctx::MacroGraph& g, const void* const (&key)[8], hipSt
     if (g.exec[victim]) (void)hipGraphExecDestroy(g.exec[victim]);
     g.exec[victim] = exec;
     g.used[victim] = ++g.tick;
-    memcpy(g.key[victim], key, sizeof(g.key[victim]));
+    g.key[victim] = key;
     return VCLA_OK;
 }
 
@@ -622,6 +631,7 @@ static int vision_forward_impl(vcla_ctx* ctx, const void* pixel_values, void* im
 
 extern "C" int vcla_vision_forward(vcla_ctx* ctx, const void* pixel_values, void* image_embeds, int B, void* ws,
                                    size_t ws_bytes, void* vit_tap, void* res_tap, void* stream) {
+    VCLA_KNOBS_SCOPE();
     VCLA_REQUIRE(ctx && ctx->finalized, VCLA_ERR_BAD_ARG, "vision_forward: context not finalized");
     VCLA_REQUIRE(pixel_values && image_embeds && ws, VCLA_ERR_BAD_ARG, "vision_forward: null pointer");
     VCLA_REQUIRE(B > 0, VCLA_ERR_BAD_SHAPE, "vision_forward: B=%d", B);
@@ -730,32 +740,29 @@ static int llama_layer(vcla_ctx* ctx, hipStream_t s, const LlamaLayer& L, const 
     // fragment-major: RMSNorm writes its output that way (vcla_rmsnorm_pack), the attention kernel stores its output that way,
     // the SwiGLU epilogue stores the activations that way; the residual stream w.x stays row-major.  7 launches per layer,
     // no split-K partials.
-    static const int ds_env = getenv("VCLA_DSTREAM") ? atoi(getenv("VCLA_DSTREAM")) : 1;
+    const vcla_knobs& kn = vcla_knobs_get();
     const bool has_frag = (L.vqkv.frag && L.vo.frag && L.vgu.frag && L.vd.frag) || (L.vqkv.q8f && L.vo.q8f && L.vgu.q8f && L.vd.q8f);
     // Decode steps only (ctx->run.decode_step): the branch leaves w.h fragment-major and un-normalised, which decode_step_impl's
     // final norm + lm_head expect and vcla_llama_prefill's all_logits tail (row-major w.h) does not -- a single-token
     // forward(input_ids[B, 1], past_key_values=cache) goes through the panel kernels below.
-    if (ds_env && ctx->run.decode_step && T == 1 && dt == VCLA_BF16 && M >= 2 && M <= 64 && has_frag && D % 32 == 0 && c.t_inter % 32 == 0) {
+    if (kn.dstream && ctx->run.decode_step && T == 1 && dt == VCLA_BF16 && M >= 2 && M <= 64 && has_frag && D % 32 == 0 && c.t_inter % 32 == 0) {
         // RMSNorm is deferred across the GEMMs (VCLA_DS_DEFER=0: a vcla_rmsnorm_pack launch per norm instead): o_proj / down_proj
         // store gamma * x fragment-major next to the residual stream plus per-row partial sums of squares, and the consuming
         // GEMM scales its accumulators by rstd(x): W . (gamma * x) * rstd = W . RMSNorm(x).  5 launches per layer.
-        static const int defer_env = getenv("VCLA_DS_DEFER") ? atoi(getenv("VCLA_DS_DEFER")) : 1;
-        const bool defer = defer_env != 0 && D % 16 == 0;
+        const bool defer = kn.ds_defer != 0 && D % 16 == 0;
         // o_proj / down_proj (N = 4096 outputs, 16 columns per workgroup) are bound by re-reading the activations (a CU ingests only
         // ~45 GB/s from L2), not by the weights: K slices per tile group cut that traffic; a parallel reduce launch finishes the
         // tiles.  Measured at M = 64 (tools/bench_kernels.py dstream): down_proj 33.2 -> 25.7 us with 4 slices, o_proj 15.7 -> 15.0
         // with 2 (4: 15.8); at M = 32 only down_proj gains (24.4 -> 21.6 us).
-        static const int sk_env = getenv("VCLA_DS_SPLITK") ? atoi(getenv("VCLA_DS_SPLITK")) : 4;
-        const int sk_o = (M > 32 && D >= 2048 && sk_env > 1) ? 2 : 0, sk_d = (M > 16 && c.t_inter >= 4096) ? sk_env : 0;
+        const int sk_o = (M > 32 && D >= 2048) ? 2 : 0, sk_d = (M > 16 && c.t_inter >= 4096) ? 4 : 0;
         const float scale_ = 1.0f / sqrtf((float)d);
         if (!(defer && h_ready)) RUN(vcla_rmsnorm_pack(w.x, D, L.ln1g, w.h, M, D, c.t_eps, s));
         // qkv: like o_proj / down_proj it is bound by every CU reading the whole activation panel -- but its consumer reads just ONE row per
         // workgroup, so the K slices need no reduce launch: the projection leaves two raw fp32 slices (6 tiles per pair of workgroups, one
         // pass over half of K each) and the attention kernel sums them while it loads q / k / v, applying the deferred-RMSNorm rstd and the
         // fp8 weight scale itself.  M > 32 (below that the panel is small), B * H >= 1024 (the 2-wave attention form), 16 partial sums per row.
-        static const int qs_env = getenv("VCLA_DS_QKV_SPLIT") ? atoi(getenv("VCLA_DS_QKV_SPLIT")) : 1;
         const bool a_def = defer && h_ready;
-        const bool qkv_split = qs_env && M > 32 && (int64_t)B * H >= 1024 && d >= 64 && ctx->run.splitk_ws && (size_t)2 * M * 3 * D * 4 <= SPLITK_WS_BYTES &&
+        const bool qkv_split = kn.ds_qkv_split && M > 32 && (int64_t)B * H >= 1024 && d >= 64 && ctx->run.splitk_ws && (size_t)2 * M * 3 * D * 4 <= SPLITK_WS_BYTES &&
                                (!a_def || ctx->run.ssq_parts == 16);
         if (qkv_split) {
             RUN(gemm_ds(ctx, s, w.h, L.wqkv, L.vqkv, nullptr, 0, w.qkv, 3 * D, nullptr, M, 3 * D, D, VCLA_EPI_NONE, 0,
@@ -837,6 +844,7 @@ static int llama_prefill_impl(vcla_ctx* ctx, const void* inputs_embeds, int B, i
 extern "C" int vcla_llama_prefill(vcla_ctx* ctx, const void* inputs_embeds, int B, int T, int pos0, void* kv_cache,
                                   int ctx_max, const int32_t* key_mask, float* logits, int all_logits, void* ws,
                                   size_t ws_bytes, void* layer_tap, void* stream) {
+    VCLA_KNOBS_SCOPE();
     VCLA_REQUIRE(ctx && ctx->finalized && ctx->c.t_layers > 0, VCLA_ERR_BAD_ARG, "llama_prefill: context not finalized, or vision-only");
     VCLA_REQUIRE(inputs_embeds && kv_cache && ws, VCLA_ERR_BAD_ARG, "llama_prefill: null pointer");
     const vcla_model_cfg& c = ctx->c;
@@ -890,14 +898,7 @@ static int llama_prefill_impl(vcla_ctx* ctx, const void* inputs_embeds, int B, i
 // The persistent decode step serves B = 1 in the bf16 mode when its weight stream is registered, no fp8 decode copies are loaded (those
 // steps read the 1-byte weights) and the device is the 256-CU part the row ownership is laid out for.  VCLA_ENGINE=0: the launch path.
 static bool engine_step_ok(const vcla_ctx* ctx, int B) {
-    const char* eng_s = getenv("VCLA_ENGINE");        // read per call: A/B runs and the tests flip it inside one process
-    const int eng_env = eng_s ? atoi(eng_s) : 1;
-    static const int n_cu = [] {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) { (void)hipGetLastError(); return 0; }
-        return n;
-    }();
-    return eng_env && B == 1 && ctx->eng_w && ctx->eng_g && ctx->c.act_dtype == VCLA_BF16 && !ctx->c.t_kv_fp8 && n_cu == EG_NCU &&
+    return vcla_knobs_get().engine && B == 1 && ctx->eng_w && ctx->eng_g && ctx->c.act_dtype == VCLA_BF16 && !ctx->c.t_kv_fp8 && ctx->n_cu == EG_NCU &&
            !(ctx->llama[0].vqkv.q8 && ctx->llama[0].vqkv.s8);
 }
 
@@ -920,30 +921,28 @@ static int decode_step_impl(vcla_ctx* ctx, hipStream_t s, const int64_t* ids_in,
         ea.logits = lg; ea.mbox = (unsigned long long*)w.eng;
         // the decode LOOP without a sampler: argmax, token record, next embedding and position advance happen inside the launch (VCLA_ENGINE_TAIL=0: the
         // two separate launches, as the loop has done since round 3)
-        const char* tail_s = getenv("VCLA_ENGINE_TAIL");
-        bool fold = loop_ids_out && !samp && ids_out == w.ids && pos_dev && !logits && (tail_s ? atoi(tail_s) != 0 : true);
+        const vcla_knobs& kn = vcla_knobs_get();
+        bool fold = loop_ids_out && !samp && ids_out == w.ids && pos_dev && !logits && kn.engine_tail != 0;
         if (fold) {
             ea.tail_ids_out = loop_ids_out; ea.tail_cur = w.ids; ea.tail_embed = (const bf16_t*)ctx->embed; ea.tail_x = (bf16_t*)w.x;
             ea.tail_pos = pos_dev; ea.tail_step_base = loop_step_base;
         }
         if (tail_folded) *tail_folded = fold;
-        { const char* e_ = getenv("VCLA_ENGINE_SPLIT"); ea.split_min = e_ ? atoi(e_) : 512; }      // VCLA_ENGINE_SPLIT=0: one CU per head at every context
-        { const char* e_ = getenv("VCLA_ENGINE_FAULT"); ea.fault = e_ ? atoi(e_) : 0; }            // test hook, see decode_engine.h
-        if (const char* tl = getenv("VCLA_ENGINE_TL")) ea.timeline = (unsigned long long*)strtoull(tl, nullptr, 16);   // debug: tools/engine_probe.py --timeline
+        ea.split_min = kn.engine_split;                              // VCLA_ENGINE_SPLIT=0: one CU per head at every context
+        ea.fault = kn.engine_fault;                                  // test hook, see decode_engine.h
+        ea.timeline = (unsigned long long*)kn.engine_tl;             // debug: tools/engine_probe.py --timeline
         RUN(vcla_engine_launch(&ea, s));
         if (fold) return VCLA_OK;
     } else {
     for (int l = 0; l < c.t_layers; ++l)   // batched mode: the norms ride on the producing GEMMs, the last one is the final norm
         RUN(llama_layer(ctx, s, ctx->llama[l], w, l, B, 1, pos0, pos_dev, kv_cache, ctx_max, key_mask, l > 0,
                         l + 1 < c.t_layers ? ctx->llama[l + 1].ln1g : ctx->norm_g));
-    static const int ds_env = getenv("VCLA_DSTREAM") ? atoi(getenv("VCLA_DSTREAM")) : 1;
     const LlamaLayer& L0 = ctx->llama[0];
-    const bool ds_layers = ds_env && dt == VCLA_BF16 && B >= 2 && B <= 64 && D % 32 == 0 && c.t_inter % 32 == 0 &&
+    const bool ds_layers = vcla_knobs_get().dstream && dt == VCLA_BF16 && B >= 2 && B <= 64 && D % 32 == 0 && c.t_inter % 32 == 0 &&
                            ((L0.vqkv.frag && L0.vo.frag && L0.vgu.frag && L0.vd.frag) || (L0.vqkv.q8f && L0.vo.q8f && L0.vgu.q8f && L0.vd.q8f));
     if (ds_layers && (ctx->vlm.frag || ctx->vlm.q8f)) {
         // streaming layers leave the residual stream in w.x: final norm -> fragment-major, lm_head streamed the same way
-        static const int defer_env = getenv("VCLA_DS_DEFER") ? atoi(getenv("VCLA_DS_DEFER")) : 1;
-        const bool defer = defer_env != 0 && D % 16 == 0;     // the last down_proj left gamma_final * x and its row statistics in w.h / w.ssq
+        const bool defer = vcla_knobs_get().ds_defer != 0 && D % 16 == 0;     // the last down_proj left gamma_final * x and its row statistics in w.h / w.ssq
         if (!defer) RUN(vcla_rmsnorm_pack(w.x, D, ctx->norm_g, w.h, B, D, c.t_eps, s));
         RUN(gemm_ds(ctx, s, w.h, ctx->lm_head, ctx->vlm, nullptr, 0, lg, c.t_vocab, nullptr, B, c.t_vocab, D, VCLA_EPI_NONE, 1,
                     defer ? w.ssq : nullptr, ctx->run.ssq_parts));
@@ -979,6 +978,7 @@ static int check_decode_args(vcla_ctx* ctx, const int64_t* ids_in, int B, int po
 extern "C" int vcla_llama_decode_step(vcla_ctx* ctx, const int64_t* ids_in, int B, int pos0, int32_t* pos_dev,
                                       int advance_pos, void* kv_cache, int ctx_max, const int32_t* key_mask,
                                       float* logits, int64_t* ids_out, void* ws, size_t ws_bytes, void* stream) {
+    VCLA_KNOBS_SCOPE();
     RUN(check_decode_args(ctx, ids_in, B, pos0, pos_dev, kv_cache, ctx_max, ws, ws_bytes));
     LlamaWs w;
     carve_llama(ctx, B, 1, (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255), &w);
@@ -999,6 +999,7 @@ extern "C" int vcla_llama_decode_loop_sampled(vcla_ctx* ctx, const int64_t* ids_
                                               void* kv_cache, int ctx_max, const int32_t* key_mask, int64_t* ids_out, void* ws,
                                               size_t ws_bytes, int use_graph, const vcla_sample_args* sampling, int n_hist0,
                                               void* stream) {
+    VCLA_KNOBS_SCOPE();
     RUN(check_decode_args(ctx, ids_in, B, pos0, pos_dev, kv_cache, ctx_max, ws, ws_bytes));
     VCLA_REQUIRE(pos_dev && ids_out && n_steps >= 0, VCLA_ERR_BAD_ARG, "llama_decode_loop: needs pos_dev, ids_out, n_steps >= 0");
     VCLA_REQUIRE(!sampling || (sampling->history && n_hist0 >= 0), VCLA_ERR_BAD_ARG, "llama_decode_loop: sampling needs the history buffer");
@@ -1042,47 +1043,38 @@ extern "C" int vcla_llama_decode_loop_sampled(vcla_ctx* ctx, const int64_t* ids_
     }
     // hipGraph path: capture one step once per (buffers, shapes) key, replay n_steps times.
     auto& k = ctx->graph_key;
+    const vcla_knobs& kn = vcla_knobs_get();
     const bool same = ctx->graph_exec && k.ids == (const void*)w.ids && k.kv == kv_cache && k.mask == (const void*)key_mask &&
                       k.ws == ws && k.out == (const void*)ids_out && k.B == B && k.pos0 == pos0 && k.ctx_max == ctx_max &&
-                      k.pos_dev == (const void*)pos_dev && k.step_base == step_base && k.has_samp == (sampling != nullptr) && k.engine == (int)engine_step_ok(ctx, B) &&
+                      k.pos_dev == (const void*)pos_dev && k.step_base == step_base && k.has_samp == (sampling != nullptr) &&
+                      memcmp(&k.knobs, &kn, sizeof kn) == 0 &&
                       (!sampling || (k.n_hist0 == n_hist0 && memcmp(&k.samp, sampling, sizeof(*sampling)) == 0));
-    // several steps per graph launch (VCLA_GRAPH_STEPS=4): measured EQUAL to one step per launch on MI355X (B = 1: 359.7 vs 359.3
-    // tok/s; the ~9 us between graph launches seen in round 1 are gone with the shorter step tail) -> off by default
-    static const int gsteps_env = getenv("VCLA_GRAPH_STEPS") ? atoi(getenv("VCLA_GRAPH_STEPS")) : 1;
-    const int G = gsteps_env > 1 ? gsteps_env : 1;
-    auto capture = [&](int count, hipGraphExec_t* out) -> int {
+    if (!same) {
+        if (ctx->graph_exec) { (void)hipGraphExecDestroy(ctx->graph_exec); ctx->graph_exec = nullptr; }
         hipGraph_t graph = nullptr;
         VCLA_CHECK_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        int rc = VCLA_OK;
-        for (int i = 0; i < count && !rc; ++i) rc = one_step(s);
+        const int rc = one_step(s);
         hipError_t ce = hipStreamEndCapture(s, &graph);
         if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
         if (ce != hipSuccess) return vcla_fail(VCLA_ERR_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(ce));
-        hipError_t ie = hipGraphInstantiate(out, graph, nullptr, nullptr, 0);
+        hipError_t ie = hipGraphInstantiate(&ctx->graph_exec, graph, nullptr, nullptr, 0);
         (void)hipGraphDestroy(graph);
-        if (ie != hipSuccess) { *out = nullptr; return vcla_fail(VCLA_ERR_HIP, "hipGraphInstantiate failed: %s", hipGetErrorString(ie)); }
-        return VCLA_OK;
-    };
-    if (!same) {
-        if (ctx->graph_exec) { (void)hipGraphExecDestroy(ctx->graph_exec); ctx->graph_exec = nullptr; }
-        if (ctx->graph_exec_multi) { (void)hipGraphExecDestroy(ctx->graph_exec_multi); ctx->graph_exec_multi = nullptr; }
-        RUN(capture(1, &ctx->graph_exec));
+        if (ie != hipSuccess) { ctx->graph_exec = nullptr; return vcla_fail(VCLA_ERR_HIP, "hipGraphInstantiate failed: %s", hipGetErrorString(ie)); }
         k.ids = w.ids; k.kv = kv_cache; k.mask = key_mask; k.ws = ws; k.out = ids_out; k.B = B; k.pos0 = pos0;
         k.ctx_max = ctx_max; k.pos_dev = pos_dev; k.step_base = step_base;
-        k.has_samp = sampling != nullptr; k.n_hist0 = n_hist0; k.engine = (int)engine_step_ok(ctx, B);
+        k.has_samp = sampling != nullptr; k.n_hist0 = n_hist0; k.knobs = kn;
         if (sampling) memcpy(&k.samp, sampling, sizeof(*sampling));
+        if (kn.macro_graph_debug) fprintf(stderr, "[vcla] decode graph %p: capture\n", (void*)&ctx->graph_exec);
+    } else if (kn.macro_graph_debug) {
+        fprintf(stderr, "[vcla] decode graph %p: replay\n", (void*)&ctx->graph_exec);
     }
-    int left = n_steps;
-    if (G > 1 && left >= G) {
-        if (!ctx->graph_exec_multi) RUN(capture(G, &ctx->graph_exec_multi));
-        for (; left >= G; left -= G) VCLA_CHECK_HIP(hipGraphLaunch(ctx->graph_exec_multi, s));
-    }
-    for (; left > 0; --left) VCLA_CHECK_HIP(hipGraphLaunch(ctx->graph_exec, s));
+    for (int left = n_steps; left > 0; --left) VCLA_CHECK_HIP(hipGraphLaunch(ctx->graph_exec, s));
     return VCLA_OK;
 }
 
 // The persistent decode step bounds every wait; a wait that ran out leaves (site code | CU << 16) in the workspace.  Synchronises the stream.
 extern "C" int vcla_llama_decode_status(vcla_ctx* ctx, int B, const void* ws, size_t ws_bytes, void* stream) {
+    VCLA_KNOBS_SCOPE();
     VCLA_REQUIRE(ctx && ctx->finalized && ctx->c.t_layers > 0 && ws && B > 0, VCLA_ERR_BAD_ARG, "llama_decode_status: bad arguments");
     VCLA_REQUIRE(ws_bytes >= vcla_llama_workspace_bytes(ctx, B, 1), VCLA_ERR_WORKSPACE, "llama_decode_status: workspace too small");
     VCLA_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));

@@ -566,20 +566,21 @@ static int panel_splitk(const vcla_gemm_args* a, int n_pad) {
     return s;
 }
 
+// most K slices of the 8-wave panel form (the measured choice of an earlier sweep)
+#define PN_KG2_MAX_SPLITK 8
+
 template <int EPI, typename OutT, int MT>
 static int launch_panel_mt(const vcla_gemm_args* a, hipStream_t s) {
     const int n_pad = (a->N + 127) / 128 * 128;
     int splitk = panel_splitk(a, n_pad);
     const int tiles_n = (a->N + PN_BN - 1) / PN_BN;
     // 8-wave form (two K groups per workgroup): fragment-major weights (bf16 or fp8), M <= 64, at most one workgroup per CU
-    static const int kg_env = getenv("VCLA_PANEL_KG") ? atoi(getenv("VCLA_PANEL_KG")) : 2;
     bool kg2 = false;
     if constexpr (MT <= 4) {
-        if (kg_env == 2 && (a->W_frag || a->W_q8_frag) && tiles_n <= 256) {
+        if ((a->W_frag || a->W_q8_frag) && tiles_n <= 256) {
             int s2 = 256 / tiles_n;                    // <= 256 workgroups: every CU gets at most one, no second round
             const int nk = a->K / GM_BK;
-            static const int s2max = getenv("VCLA_PANEL_S2MAX") ? atoi(getenv("VCLA_PANEL_S2MAX")) : 8;
-            if (s2 > s2max) s2 = s2max;
+            if (s2 > PN_KG2_MAX_SPLITK) s2 = PN_KG2_MAX_SPLITK;
             if (s2 > nk / 2) s2 = nk / 2 > 0 ? nk / 2 : 1;   // each K group wants at least one tile
             while (s2 > 1 && (size_t)s2 * a->M * n_pad * 4 > a->splitk_ws_bytes) --s2;
             if (!a->splitk_ws) s2 = 1;
@@ -1112,16 +1113,14 @@ static int launch_mfma(const vcla_gemm_args* a, hipStream_t s) {
     const int tiles = tiles_m * tiles_n, nk = a->K / GM_BK;
     // Few tiles, long K (one image through the ViT: 24 - 96 tiles on 256 CUs, 16 - 64 serial K steps): split K so that ~256
     // workgroups run >= 4 K steps each; fp32 partial tiles + the panel kernel's reduce launch.  VCLA_MFMA128_SPLITK=0: off.
-    static const int sk_env = getenv("VCLA_MFMA128_SPLITK") ? atoi(getenv("VCLA_MFMA128_SPLITK")) : 1;
+    const int sk_env = vcla_knobs_get().mfma128_splitk;
     // Round 4: also for 129 - 255 tiles (a 129 - 256-row decode batch: qkv = 192 tiles -> 2 slices) and with a post-norm request (o_proj /
     // down_proj of those batches: 64 tiles ran 64 serial K steps on 64 CUs = 153 us; the wrapper's rmsnorm launch follows the reduce).
-    static const int s_force = getenv("VCLA_MFMA128_S") ? atoi(getenv("VCLA_MFMA128_S")) : 0;     // experiments: force the slice count
     int S = 1;
     if (sk_env && a->splitk_ws && tiles < 256 && nk >= 8) {
         const int n_pad = (a->N + 127) / 128 * 128;
         S = (256 + tiles - 1) / tiles;
         if (tiles <= 64 && a->M > 128) S *= 2;       // one 128-row pair of tiles per 128 columns: fill both workgroup slots of every CU
-        if (s_force > 0) S = s_force;
         if (S > nk / 4) S = nk / 4;
         if (S > 8) S = 8;
         while (S > 1 && (size_t)S * a->M * n_pad * 4 > a->splitk_ws_bytes) --S;
@@ -1218,6 +1217,7 @@ static int dispatch_epi(const vcla_gemm_args* a, int dtype, int kernel, hipStrea
 static int gemm_impl(const vcla_gemm_args* a, int dtype, void* stream);
 
 extern "C" int vcla_gemm(const vcla_gemm_args* a, int dtype, void* stream) {
+    VCLA_KNOBS_SCOPE();
     VCLA_REQUIRE(a, VCLA_ERR_BAD_ARG, "gemm: null args");
     if (a->post_norm_gamma) {
         VCLA_REQUIRE(a->post_norm_out && a->epilogue == VCLA_EPI_NONE && !a->out_f32 && a->c_group_rows <= 0 && a->N <= PN_NORM_MAX &&
@@ -1261,9 +1261,8 @@ static int gemm_impl(const vcla_gemm_args* a, int dtype, void* stream) {
             // the resampler's 64 latent rows (K = 1024: q / kv / out / fc1): one launch of 64 x 64 ring tiles instead of K slices + a reduce launch
             // (graph-replayed, rotating weights, M = 64: 15.8 - 18.0 -> 13.0 - 13.3 us; K = 4096 (fc2) stays: 19.2 vs 26.0).  The decode-side
             // twins (W_frag / W_q8_frag: LLaMA rows) keep their kernels.
-            static const int ring_env = getenv("VCLA_RING") ? atoi(getenv("VCLA_RING")) : 1;
-            const char* rv_ = getenv("VCLA_RING_VIT"); const int ring_vit_env = rv_ ? atoi(rv_) : 1;      // read per call: tools/bench_kernels.py vit1 flips it
-            if (ring_env && ring_vit_env && a->M > 16 && a->K <= 2048 && a->N >= 512 && !a->W_frag && !a->W_q8_frag && !a->W_q8 && !a->norm_gamma && !a->out_f32 &&
+            const vcla_knobs& kn = vcla_knobs_get();
+            if (kn.ring && kn.ring_vit && a->M > 16 && a->K <= 2048 && a->N >= 512 && !a->W_frag && !a->W_q8_frag && !a->W_q8 && !a->norm_gamma && !a->out_f32 &&
                 a->epilogue != VCLA_EPI_SWIGLU && a->c_group_rows <= 0 && a->A) kernel = 11;
         }
         else {
@@ -1274,9 +1273,7 @@ static int gemm_impl(const vcla_gemm_args* a, int dtype, void* stream) {
                 vcla_gemm_args head = *a, tail = *a;
                 head.M = a->M - rem;
                 if (prefer_256(&head)) {
-                    static const int pf_env = getenv("VCLA_GEMM_PF") ? atoi(getenv("VCLA_GEMM_PF")) : 1;
-                    static const int xr_env = getenv("VCLA_GEMM_XR") ? atoi(getenv("VCLA_GEMM_XR")) : 1;
-                    if (pf_env && xr_env && vcla_gemm_tile257_ok(a) && a->K >= 3 * GM_BK) {
+                    if (vcla_knobs_get().gemm_pf && vcla_knobs_get().gemm_xr && vcla_gemm_tile257_ok(a) && a->K >= 3 * GM_BK) {
                         // M = B * 257: ONE launch of 257-row tiles instead of whole 256-row rounds + a tail launch
                         head = *a;
                         head.force_kernel = 4;
@@ -1291,9 +1288,8 @@ static int gemm_impl(const vcla_gemm_args* a, int dtype, void* stream) {
                     head.force_kernel = 4;
                     // the tail: one launch of the skinny kernel (intra-workgroup split-K, epilogue in the kernel) for short K, the split-K
                     // panel kernel + its reduce launch for long K.  Measured at 64 rows (tools/bench_kernels.py vittail): K = 1024:
-                    // 9.7 - 10.8 us vs 11.6 - 13.6 us; K = 4096: 28.1 vs 15.6 us.  VCLA_TAIL_KERNEL = 7 / 8 forces one form.
-                    static const int tail_env = getenv("VCLA_TAIL_KERNEL") ? atoi(getenv("VCLA_TAIL_KERNEL")) : 0;
-                    if (!a->post_norm_gamma && (tail_env == 7 || (tail_env == 0 && a->K <= 2048))) tail.force_kernel = 7;
+                    // 9.7 - 10.8 us vs 11.6 - 13.6 us; K = 4096: 28.1 vs 15.6 us.
+                    if (!a->post_norm_gamma && a->K <= 2048) tail.force_kernel = 7;
                     head.post_norm_gamma = tail.post_norm_gamma = nullptr;   // the wrapper normalises all of C afterwards
                     int rc = gemm_impl(&head, dtype, stream);
                     return rc ? rc : gemm_impl(&tail, dtype, stream);
@@ -1302,13 +1298,12 @@ static int gemm_impl(const vcla_gemm_args* a, int dtype, void* stream) {
             kernel = prefer_256(a) ? 4 : 1;
             // 129 - 256 rows (a LLaMA decode batch of that many sequences, a prefill of that many prompt rows): the intake-bound ring kernel
             // (gemm_ring.hip) -- full K per tile, no split-K partials.  VCLA_RING=0: the round-4 dispatch (128 x 128 tiles + K slices).
-            static const int ring_env = getenv("VCLA_RING") ? atoi(getenv("VCLA_RING")) : 1;
-            if (ring_env && a->M <= 256 && (a->epilogue == VCLA_EPI_NONE || (a->epilogue == VCLA_EPI_SWIGLU && !a->out_f32)) && a->c_group_rows <= 0) kernel = 11;
+            const vcla_knobs& kn = vcla_knobs_get();
+            if (kn.ring && a->M <= 256 && (a->epilogue == VCLA_EPI_NONE || (a->epilogue == VCLA_EPI_SWIGLU && !a->out_f32)) && a->c_group_rows <= 0) kernel = 11;
             // ONE image through the ViT (257 rows, K = 1024: qkv / out / fc1): 72 - 96 tiles of 128 x 128 needed K slices + a reduce launch to fill the chip; 64 x 64
             // (128 x 96) ring tiles over the full K fill it in one launch with the bias / GELU / residual in the tile's epilogue.  Graph-replayed, rotating weights,
             // M = 257: qkv 25.4 -> 14.0 us, out 17.8 -> 13.5, fc1 28.0 -> 18.0; fc2 (K = 4096) stays on the K slices (24.2 vs 26.2).  VCLA_RING_VIT=0: off.
-            const char* rv_ = getenv("VCLA_RING_VIT"); const int ring_vit_env = rv_ ? atoi(rv_) : 1;      // read per call: tools/bench_kernels.py vit1 flips it
-            if (ring_env && ring_vit_env && a->M <= 320 && a->K <= 2048 && !a->out_f32 && a->epilogue != VCLA_EPI_SWIGLU && a->c_group_rows <= 0 && a->A && !a->W_q8) kernel = 11;
+            if (kn.ring && kn.ring_vit && a->M <= 320 && a->K <= 2048 && !a->out_f32 && a->epilogue != VCLA_EPI_SWIGLU && a->c_group_rows <= 0 && a->A && !a->W_q8) kernel = 11;
         }
     }
     VCLA_REQUIRE(kernel >= 1 && kernel <= 14, VCLA_ERR_BAD_ARG, "gemm: bad force_kernel %d", a->force_kernel);

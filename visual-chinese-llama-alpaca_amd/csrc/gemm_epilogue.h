@@ -195,22 +195,14 @@ __device__ __forceinline__ void gemm_epilogue(const vcla_gemm_args& a, f32x4_t (
 #pragma unroll
                 for (int p = 0; p < NOUT / 2; ++p) {
                     float v0[4], v1[4];
-#if defined(VCLA_G2_EPI_ABLATE) && VCLA_G2_EPI_ABLATE == 2     // timing experiment: raw accumulators, no bias / activation / residual
-                    for (int r = 0; r < 4; ++r) { v0[r] = acc[i][2 * p][r]; v1[r] = acc[i][2 * p + 1][r]; }
-#else
                     tile_vals(i, 2 * p, m, ascale, v0);
                     tile_vals(i, 2 * p + 1, m, ascale, v1);
-#endif
                     unsigned a0 = pack_bf2(v0[0], v0[1]), a1 = pack_bf2(v0[2], v0[3]);
                     unsigned b0 = pack_bf2(v1[0], v1[1]), b1 = pack_bf2(v1[2], v1[3]);
                     const auto s0 = __builtin_amdgcn_permlane16_swap(a0, b0, false, false);
                     const auto s1 = __builtin_amdgcn_permlane16_swap(a1, b1, false, false);
                     const int n = n_first + (2 * p + (row_ & 1)) * 16 + (row_ >> 1) * 8;
-#if defined(VCLA_G2_EPI_ABLATE) && VCLA_G2_EPI_ABLATE == 1     // timing experiment: everything but the store itself
-                    asm volatile("" :: "v"(s0[0]), "v"(s1[0]), "v"(s0[1]), "v"(s1[1]), "v"(n), "v"(crow));
-#else
                     *reinterpret_cast<uint4*>(Cg + crow * a.ldc + n) = make_uint4(s0[0], s1[0], s0[1], s1[1]);
-#endif
                 }
             }
             return;

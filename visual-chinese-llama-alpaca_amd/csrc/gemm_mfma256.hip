@@ -38,8 +38,6 @@ template <int N> __device__ __forceinline__ void g2_vmcnt() { asm volatile("s_wa
 __device__ unsigned long long* g2_timeline = nullptr;      // [workgroup][8]: entry, first slab landed, K loop done, epilogue issued, stores drained
 extern "C" int vcla_debug_set_timeline(unsigned long long* p) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(g2_timeline), &p, sizeof(p)); }
 #define G2_STAMP(i_) do { if (g2_timeline && threadIdx.x == 0) g2_timeline[(size_t)blockIdx.x * 8 + (i_)] = wall_clock64(); } while (0)
-// K-loop ablations are COMPILE-time (-DVCLA_G2_ABLATE=1/2/3; results are garbage): 1 = no fragment reads (MFMA + DMA only), 2 = no MFMAs
-// (LDS reads + DMA only), 3 = no DMA after the first slab (MFMA + LDS reads only).  (A run-time switch wrecked the loop's code.)
 #else
 #define G2_STAMP(i_) do { } while (0)
 #endif
@@ -100,11 +98,10 @@ __global__ __launch_bounds__(512) void gemm_mfma256_kernel(vcla_gemm_args a, int
     const int frow = lane & 15, fch = lane >> 4;
     const int nk = a.K / GM_BK;
 
-    // Optionally persistent over output tiles (VCLA_GEMM_PERSIST=1: grid = 256, tile id = blockIdx.x, + gridDim.x, ...; the
-    // XCD-aware order of tile_assign is kept because the grid is a multiple of 8): the FIRST K slab of the next tile is requested
-    // during the last K step of the current one, so its latency and the drain of the epilogue's stores overlap instead of
-    // opening every tile with a cold fetch.  Measured on MI355X: no difference (the per-round overhead is not the cold fetch),
-    // so the default launch stays one workgroup per tile.
+    // Written persistent over output tiles (a grid of 256 would walk tile id = blockIdx.x, + gridDim.x, ...; the XCD-aware order
+    // of tile_assign holds for any grid that is a multiple of 8): the FIRST K slab of the next tile is requested during the last K
+    // step of the current one.  Measured on MI355X: no difference against one workgroup per tile (the per-round overhead is not
+    // the cold fetch), so the launch is one workgroup per tile and the loop runs once.
     int tile = blockIdx.x;
     int tm, tn;
     tile_assign(tile, tiles_m, tiles_n, 4, tm, tn);
@@ -282,9 +279,6 @@ __global__ __launch_bounds__(512) void gemm_mfma256_kernel(vcla_gemm_args a, int
             const int cur = (kt + p0) & 1;
             __syncthreads();  // (compiler adds vmcnt(0)): slab kt has landed for every wave, and buffer cur^1 is no longer read
             if (kt == 0) G2_STAMP(1);
-#if defined(VCLA_G2_ABLATE) && VCLA_G2_ABLATE == 3
-            if (kt >= 1) { /* no more DMA */ } else
-#endif
             if (kt + 1 < nk) {
                 issue(kt + 1, cur ^ 1);
             } else if (has_next) {   // last K step: the staging pointers of this tile are dead -> re-aim them at the next tile
@@ -299,30 +293,16 @@ __global__ __launch_bounds__(512) void gemm_mfma256_kernel(vcla_gemm_args a, int
             for (int kk = 0; kk < 2; ++kk) {
                 bf16x8_t wf[4];
                 bf16x8_t af[8];
-#if defined(VCLA_G2_ABLATE) && VCLA_G2_ABLATE == 1
-#pragma unroll
-                for (int j = 0; j < 4; ++j) { wf[j] = __builtin_bit_cast(bf16x8_t, acc[j][0]); asm volatile("" : "+v"(wf[j])); }
-#pragma unroll
-                for (int i = 0; i < 8; ++i) { af[i] = __builtin_bit_cast(bf16x8_t, acc[i][1]); asm volatile("" : "+v"(af[i])); }
-#else
 #pragma unroll
                 for (int j = 0; j < 4; ++j) wf[j] = *reinterpret_cast<const bf16x8_t*>(Ws + lds_off(wn * 64 + j * 16 + frow, kk * 4 + fch));
 #pragma unroll
                 for (int i = 0; i < 8; ++i)
                     af[i] = *reinterpret_cast<const bf16x8_t*>(As + lds_off(wm * 128 + i * 16 + frow, kk * 4 + fch));
-#endif
-#if defined(VCLA_G2_ABLATE) && VCLA_G2_ABLATE == 2
-#pragma unroll
-                for (int j = 0; j < 4; ++j) asm volatile("" :: "v"(wf[j]));      // keep the reads live (guide rule 17)
-#pragma unroll
-                for (int i = 0; i < 8; ++i) asm volatile("" :: "v"(af[i]));
-#else
 #pragma unroll
                 for (int i = 0; i < 8; ++i)
 #pragma unroll
                     for (int j = 0; j < 4; ++j)
                         acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j], af[i], acc[i][j], 0, 0, 0);
-#endif
                 if (SGB) {
                     // issue order: 6 fragment reads (4 W + 2 A), then 4 MFMAs per further A read, so every ds_read runs
                     // two fragments ahead of the MFMAs that consume it
@@ -454,9 +434,7 @@ static int launch_mfma256_fp8(const vcla_gemm_args* a, hipStream_t s) {
     auto kern = gemm_mfma256_fp8_kernel<EPI, OutT>;
     static bool attr_set[VCLA_MAX_DEVICES] = {};   // per instantiation and device
     { const int rc_ = vcla_raise_dyn_lds((const void*)kern, lds, attr_set); if (rc_) return rc_; }
-    static const int pg8 = getenv("VCLA_GEMM_PERSIST") ? atoi(getenv("VCLA_GEMM_PERSIST")) : 0;   // measured equal (see gemm_mfma256_kernel)
-    const int nt8 = tiles_m * tiles_n;
-    kern<<<(pg8 && nt8 > 256) ? 256 : nt8, 512, lds, s>>>(*a, tiles_m, tiles_n, n_pad);   // one workgroup per CU, persistent over tiles
+    kern<<<tiles_m * tiles_n, 512, lds, s>>>(*a, tiles_m, tiles_n, n_pad);   // one workgroup per tile
     VCLA_CHECK_LAUNCH("gemm_mfma256_fp8_kernel");
     return VCLA_OK;
 }
@@ -475,10 +453,9 @@ static int launch_mfma256(const vcla_gemm_args* a, hipStream_t s) {
     auto kern = gemm_mfma256_kernel<EPI, OutT, SGB>;
     static bool attr_set[VCLA_MAX_DEVICES] = {};   // per instantiation and device
     { const int rc_ = vcla_raise_dyn_lds((const void*)kern, lds, attr_set); if (rc_) return rc_; }
-    static const int pg = getenv("VCLA_GEMM_PERSIST") ? atoi(getenv("VCLA_GEMM_PERSIST")) : 0;   // measured equal: ViT fc1 180 vs 182 us, LLaMA gate/up 1288 vs 1265 us
     // PF (default since round 3: B = 64 prefill 98.4 -> 92.4 ms, vision stack 15.8 -> 15.3 ms in the model; VCLA_GEMM_PF=0 = the plain form)
-    static const int pf = getenv("VCLA_GEMM_PF") ? atoi(getenv("VCLA_GEMM_PF")) : 1;
-    static const int xr_env = getenv("VCLA_GEMM_XR") ? atoi(getenv("VCLA_GEMM_XR")) : 1;   // 0: 256-row tiles also when M % 257 == 0
+    const int pf = vcla_knobs_get().gemm_pf;
+    const int xr_env = vcla_knobs_get().gemm_xr;   // 0: 256-row tiles also when M % 257 == 0
     const int nt = tiles_m * tiles_n;
     if (!(pf && SGB) && (a->A_slab || a->W_slab)) return vcla_fail(VCLA_ERR_BAD_ARG, "gemm: slab-major operands need the direct-to-LDS form of the 256 x 256 kernel (force_kernel 4, VCLA_GEMM_PF=1)");
     if (pf && SGB && a->K >= 3 * GM_BK) {   // force_kernel 5 (SGB = false) stays the plain form: both forms remain under test
@@ -499,7 +476,7 @@ static int launch_mfma256(const vcla_gemm_args* a, hipStream_t s) {
         VCLA_CHECK_LAUNCH("gemm_mfma256_kernel<PF>");
         return VCLA_OK;
     }
-    kern<<<(pg && nt > 256) ? 256 : nt, 512, lds, s>>>(*a, tiles_m, tiles_n, n_pad);   // one workgroup per CU, persistent over tiles
+    kern<<<nt, 512, lds, s>>>(*a, tiles_m, tiles_n, n_pad);   // one workgroup per tile
     VCLA_CHECK_LAUNCH("gemm_mfma256_kernel");
     return VCLA_OK;
 }

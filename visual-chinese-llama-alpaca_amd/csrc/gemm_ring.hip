@@ -234,8 +234,7 @@ __global__ __launch_bounds__(512) void gemm_ring_kernel(vcla_gemm_args a, int ti
 template <int EPI, typename OutT, int BM, int BN, int WM, int WN, int NS, int KS, bool W8, bool WF = false>
 static int launch_ring_cfg(const vcla_gemm_args* a, hipStream_t s) {
     if constexpr (!W8 && !WF && sizeof(OutT) == 2) {          // bf16 output, bf16 weights with a fragment-major twin: its pieces are contiguous KiBs (VCLA_RING_WF=0: row-major pieces)
-        static const int wf_env = getenv("VCLA_RING_WF") ? atoi(getenv("VCLA_RING_WF")) : 1;
-        if (wf_env && a->W_frag && !a->W_slab) return launch_ring_cfg<EPI, OutT, BM, BN, WM, WN, NS, KS, false, true>(a, s);
+        if (vcla_knobs_get().ring_wf && a->W_frag && !a->W_slab) return launch_ring_cfg<EPI, OutT, BM, BN, WM, WN, NS, KS, false, true>(a, s);
     }
     constexpr size_t lds = (size_t)NS * KS * BM * 128 + (size_t)(NS + (W8 ? 1 : 0)) * KS * (W8 ? BN * 64 : BN * 128) + (W8 ? (size_t)2 * KS * BN * 128 : 0) + 1024;
     static_assert(lds <= 160 * 1024, "ring exceeds the 160 KiB of a CU");
@@ -274,8 +273,7 @@ static int launch_ring(const vcla_gemm_args* a, hipStream_t s) {
     else {
         if (cfg == 2) return launch_ring_cfg<EPI, OutT, 128, 96, 4, 2, 5, 1, W8>(a, s);
         if constexpr (!W8) {      // bf16 weights: 9 single-slab stages (128 KiB in flight) instead of 4 double-slab ones (96 KiB): measured equal (+2 %); VCLA_RING_C3=0: the first form
-            static const int c3_env = getenv("VCLA_RING_C3") ? atoi(getenv("VCLA_RING_C3")) : 1;
-            if (c3_env) return launch_ring_cfg<EPI, OutT, 64, 64, 4, 2, 9, 1, W8>(a, s);
+            if (vcla_knobs_get().ring_c3) return launch_ring_cfg<EPI, OutT, 64, 64, 4, 2, 9, 1, W8>(a, s);
         }
         return launch_ring_cfg<EPI, OutT, 64, 64, 4, 2, 4, 2, W8>(a, s);
     }

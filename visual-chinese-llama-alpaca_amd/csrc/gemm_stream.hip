@@ -387,10 +387,10 @@ int vcla_gemm_dstream_launch(const vcla_gemm_args* a, hipStream_t s) {
     const bool swiglu = a->epilogue == VCLA_EPI_SWIGLU;
     const int tiles = (a->N + 15) / 16;                        // W_frag rows exist up to N_pad (multiple of 128) >= tiles * 16
     const int units = swiglu ? tiles / 2 : tiles;              // SwiGLU: N % 32 == 0
-    static const int grid_env = getenv("VCLA_DS_GRID") ? atoi(getenv("VCLA_DS_GRID")) : 256;   // one workgroup per CU
-    int grid = units < grid_env ? units : grid_env;
+    constexpr int DS_GRID = 256;                               // one workgroup per CU
+    int grid = units < DS_GRID ? units : DS_GRID;
     if (a->ds_splitk > 1) {   // groups of ds_splitk workgroups share a tile range: keep the launch at one workgroup per CU
-        int groups = grid_env / a->ds_splitk;
+        int groups = DS_GRID / a->ds_splitk;
         if (groups < 1) groups = 1;
         if (groups > units) groups = units;
         grid = groups * a->ds_splitk;

@@ -232,14 +232,14 @@ static int launch_gemv1p(const vcla_gemm_args* a, hipStream_t s) {
     const int n_pad = (a->N + 127) / 128 * 128;
     // persistent grid: every CU gets as many workgroups as fit at once (registers / LDS of THIS instance), at most 3
     // (measured on MI355X, tools/bench_kernels.py gemv1: 7B gate/up 30.7 / 30.3 / 29.3 us at 1 / 2 / 3 per CU)
-    static const int occ_env = getenv("VCLA_GEMV_OCC") ? atoi(getenv("VCLA_GEMV_OCC")) : 3;
+    static constexpr int GV_MAX_PER_CU = 3;   // workgroups per CU at most
     static const int per_cu = [] {
         int occ = 0, dev = 0;
         hipDeviceProp_t prop;
         if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 512;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, gemv1p_kernel<R, K, SWIGLU, FP8, OutT>, GV_WPB * 64, (size_t)(KP + GV_WPB) * 4) != hipSuccess || occ < 1)
             occ = 1;
-        return prop.multiProcessorCount * (occ < occ_env ? occ : occ_env);
+        return prop.multiProcessorCount * (occ < GV_MAX_PER_CU ? occ : GV_MAX_PER_CU);
     }();
     int grid = (units + GV_WPB - 1) / GV_WPB;
     if (grid > per_cu) grid = per_cu;
@@ -265,8 +265,7 @@ static int launch_gemv1p_k(const vcla_gemm_args* a, hipStream_t s) {
 // returns VCLA_OK (or a launch error) when it handled the call, -1 when this K has no compiled instance or the matrix is too
 // large for one buffer descriptor (the caller falls back to gemv1_kernel)
 int vcla_gemv1x_launch(const vcla_gemm_args* a, hipStream_t s) {
-    static const int on = getenv("VCLA_GEMV1X") ? atoi(getenv("VCLA_GEMV1X")) : 1;
-    if (!on || a->M != 1 || !(a->W || (a->W_q8 && a->w_scale))) return -1;
+    if (!vcla_knobs_get().gemv1x || a->M != 1 || !(a->W || (a->W_q8 && a->w_scale))) return -1;
     if ((int64_t)((a->N + 127) / 128 * 128) * a->K * 2 >= (int64_t)1 << 31) return -1;
     switch (a->K) {
         case 4096: return launch_gemv1p_k<4096>(a, s);

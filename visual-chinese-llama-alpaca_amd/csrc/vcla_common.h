@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <stdarg.h>
 #include "../../include/visualcla_hip.h"
+#include "vcla_knobs.h"
 
 typedef uint16_t bf16_t;  // raw bfloat16 bits
 

@@ -18,7 +18,6 @@ and the flat `vision_model.*` of transformers 5.x.
 """
 from __future__ import annotations
 
-import os
 from typing import Callable, Dict
 
 import torch
@@ -206,10 +205,7 @@ def add_engine_stream(packed: Dict[str, torch.Tensor], hidden: int, heads: int, 
     lmp[vocab:] = 0
     stream[:, n_layers * SL:] = lmp.view(N, s_lm, 2 * D)
     gam = [packed[f"llama.l{l}.ln{i}.g"] for l in range(n_layers) for i in (1, 2)] + [packed["llama.norm.g"]]
-    if os.environ.get("VCLA_ENGINE_LAYOUT", "slot") == "cu":        # A/B only (tools/debug/engine_variance.py): the first form of round 6, every CU's run contiguous
-        packed["llama.engine.w.cu"] = stream
-    else:
-        packed["llama.engine.w"] = stream.permute(1, 0, 2).contiguous()
+    packed["llama.engine.w"] = stream.permute(1, 0, 2).contiguous()
     packed["llama.engine.g"] = torch.stack(gam, 0).to(torch.float32).contiguous()
     return packed
 
