@@ -437,6 +437,61 @@ int vcla_llama_decode_loop_sampled(vcla_ctx* ctx, const int64_t* ids_in, int B, 
    always when the steps ran as separate launches (VCLA_ENGINE=0, other batch sizes, fp8 weights). */
 int vcla_llama_decode_status(vcla_ctx* ctx, int B, const void* ws, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------- prompt-lookup decoding (greedy, B = 1)
+   HF generate(prompt_lookup_num_tokens=k) (hf generation/utils.py _assisted_decoding with PromptLookupCandidateGenerator,
+   transformers/generation/candidate_generator.py get_candidates), reached through models/visualcla/modeling_visualcla.py:382-391.
+   One ITERATION feeds R = k + 1 rows (the last token, then k drafts looked up in the history) through the decoder in one pass over the
+   weights, takes the argmax of every row, accepts the leading drafts that equal the argmax of the row before them, emits those plus one
+   bonus token and builds the next row.  The tokens are exactly greedy decoding's; only the number of weight passes changes. */
+#define VCLA_LOOKUP_MAX_ROWS 16
+#define VCLA_LOOKUP_MAX_EOS 4
+/* int32 words of vcla_lookup_args.state */
+#define VCLA_LOOKUP_NHIST 0     /* history length                                        */
+#define VCLA_LOOKUP_COUNT 1     /* tokens emitted into out[]                              */
+#define VCLA_LOOKUP_DONE 2      /* 1 once an eos was emitted or the budget is used up     */
+#define VCLA_LOOKUP_ITERS 3     /* verify iterations that emitted                         */
+#define VCLA_LOOKUP_ACCEPTED 4  /* drafts accepted over those iterations                  */
+#define VCLA_LOOKUP_DRAFTS 5    /* drafts found for the current row (the rest is filler)  */
+#define VCLA_LOOKUP_STATE_WORDS 8
+typedef struct vcla_lookup_args {
+    int k;                      /* drafts per iteration, 1 .. VCLA_LOOKUP_MAX_ROWS - 1                          */
+    int ngram_max;              /* max_matching_ngram_size (HF default 2)                                       */
+    int budget;                 /* tokens out[] may hold in all (max_new_tokens)                                */
+    int n_eos;
+    int eos_ids[VCLA_LOOKUP_MAX_EOS];  /* an eos ends the output and is never drafted                        */
+    int hist_cap;               /* capacity of history[]                                                        */
+    int64_t filler;             /* id padding the row when fewer than k drafts are found; < 0: the last token   */
+    int64_t* row;               /* device [k + 1]: the next input row (the last emitted token, then the drafts)  */
+    int64_t* history;           /* device [hist_cap]: the ids the drafts are looked up in                       */
+    int64_t* out;               /* device [budget]: emitted tokens                                              */
+    int32_t* state;             /* device [VCLA_LOOKUP_STATE_WORDS], see above                                  */
+} vcla_lookup_args;
+
+/* The attention of one verify pass (the R-row instance of LlamaAttention.forward hf:llama/modeling_llama.py:217-281 against the cache):
+   qkv [R, 3 H d] (act dtype, row-major) of ONE sequence at positions p .. p + R - 1, p = pos0 + *pos_dev.  RoPE on q and k, the R new
+   K / V rows appended to the cache ([H][ctx_max][d] per K and V), row j attends over keys [0, p + j] minus the key_mask holes.  out:
+   [R, H d] row-major, or (out_frag, bf16) the fragment-major layout of the streaming GEMMs.  Rows at positions >= ctx_max are neither
+   written nor meaningful.  scratch: vcla_attn_verify_scratch_bytes (0 for ctx_max <= 256) of device memory. */
+size_t vcla_attn_verify_scratch_bytes(int H, int d, int ctx_max);
+int vcla_attn_verify(const void* qkv, void* k_cache, void* v_cache, const float* cos_tab, const float* sin_tab, void* out, int R, int H,
+                     int d, int ctx_max, int pos0, const int32_t* pos_dev, const int32_t* key_mask, float scale, int dtype, int out_frag,
+                     void* scratch, size_t scratch_bytes, void* stream);
+
+/* The bookkeeping of one iteration (the loop body of hf _assisted_decoding after the target forward, greedy: `n_matches`, the token
+   append, and the next PromptLookupCandidateGenerator.get_candidates call).  argmax_ids [k + 1] (device) of the verify rows; NULL: only
+   build args->row from the history (the first row of a loop).  Emits, advances *pos_dev by the number emitted, sets the done word. */
+int vcla_lookup_step(const int64_t* argmax_ids, const vcla_lookup_args* args, int32_t* pos_dev, void* stream);
+
+/* Workspace of vcla_llama_verify_loop (covers the decoder rows, logits, argmax ids and the attention scratch). */
+size_t vcla_llama_verify_workspace_bytes(const vcla_ctx* ctx, int ctx_max);
+
+/* n_iters verify iterations at B = 1: embed args->row, the decoder over its k + 1 rows at positions pos0 + *pos_dev .., final norm +
+   lm_head, argmax per row, vcla_lookup_step.  Everything is enqueued on `stream`; use_graph != 0 captures one iteration (own graph
+   slot: the decode loop's cached graph stays) and replays it.  Bf16 or fp32 activations, bf16 K / V cache (not VCLA_KV_FP8).  The caller
+   sizes ctx_max >= pos0 + budget + k (the rows of the last pass stay inside the cache). */
+int vcla_llama_verify_loop(vcla_ctx* ctx, const vcla_lookup_args* args, int pos0, int32_t* pos_dev, int n_iters, void* kv_cache,
+                           int ctx_max, const int32_t* key_mask, void* ws, size_t ws_bytes, int use_graph, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

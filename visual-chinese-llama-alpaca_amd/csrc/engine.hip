@@ -145,6 +145,9 @@ struct vcla_ctx {
         void* q8_ws = nullptr;         // fp8 activation staging of the running prefill (t_fp8_mfma), else NULL
         float* q8s_ws = nullptr;
         int ssq_parts = 0;             // layout of the deferred-RMSNorm row statistics the last producer wrote (see gemm_ds)
+        bool verify = false;           // inside verify_iter_impl: the T rows of llama_layer are one sequence's verify rows (vcla_attn_verify)
+        void* verify_scratch = nullptr;
+        size_t verify_scratch_bytes = 0;
     } run;
     // cached graphs of the vision stack and of the prefill (fixed launch sequences per shape: ~250 / ~290 launches that are host-bound
     // at B = 1).  Keyed on every pointer and shape the captured launches bake in and on the switch snapshot that chose them; see run_macro.
@@ -171,6 +174,14 @@ struct vcla_ctx {
         vcla_sample_args samp;
         vcla_knobs knobs;
     } graph_key = {};
+    // cached prompt-lookup graph: one verify iteration (its own slot, so that a plain generate() afterwards still replays graph_exec)
+    hipGraphExec_t lookup_exec = nullptr;
+    struct {
+        const void *kv, *mask, *ws, *pos_dev;
+        int pos0, ctx_max;
+        vcla_lookup_args args;
+        vcla_knobs knobs;
+    } lookup_key = {};
 };
 
 static inline int pad_to(int x, int m) { return (x + m - 1) / m * m; }
@@ -215,11 +226,12 @@ extern "C" int vcla_ctx_create(const vcla_model_cfg* cfg, vcla_ctx** out) {
 static void drop_graphs(vcla_ctx* ctx) {
     // An exec may still be executing (its last hipGraphLaunch is asynchronous) and HIP does not promise deferred destruction on every ROCm
     // version: drain the device first.  Only when there is something to destroy -- registering the tensors of a fresh context costs nothing.
-    bool any = ctx->graph_exec != nullptr;
+    bool any = ctx->graph_exec != nullptr || ctx->lookup_exec != nullptr;
     for (const vcla_ctx::MacroGraph* g : {&ctx->vision_graph, &ctx->prefill_graph})
         for (int i = 0; i < vcla_ctx::MacroGraph::kSlots; ++i) any = any || g->exec[i];
     if (any && hipDeviceSynchronize() != hipSuccess) (void)hipGetLastError();
     if (ctx->graph_exec) { (void)hipGraphExecDestroy(ctx->graph_exec); ctx->graph_exec = nullptr; }
+    if (ctx->lookup_exec) { (void)hipGraphExecDestroy(ctx->lookup_exec); ctx->lookup_exec = nullptr; }
     for (vcla_ctx::MacroGraph* g : {&ctx->vision_graph, &ctx->prefill_graph}) {
         for (int i = 0; i < vcla_ctx::MacroGraph::kSlots; ++i)
             if (g->exec[i]) { (void)hipGraphExecDestroy(g->exec[i]); g->exec[i] = nullptr; }
@@ -745,7 +757,8 @@ static int llama_layer(vcla_ctx* ctx, hipStream_t s, const LlamaLayer& L, const 
     // Decode steps only (ctx->run.decode_step): the branch leaves w.h fragment-major and un-normalised, which decode_step_impl's
     // final norm + lm_head expect and vcla_llama_prefill's all_logits tail (row-major w.h) does not -- a single-token
     // forward(input_ids[B, 1], past_key_values=cache) goes through the panel kernels below.
-    if (kn.dstream && ctx->run.decode_step && T == 1 && dt == VCLA_BF16 && M >= 2 && M <= 64 && has_frag && D % 32 == 0 && c.t_inter % 32 == 0) {
+    const bool verify = ctx->run.verify;   // B = 1, T = k + 1 verify rows at pos0 + *pos_dev (vcla_llama_verify_loop)
+    if (kn.dstream && ctx->run.decode_step && (T == 1 || verify) && dt == VCLA_BF16 && M >= 2 && M <= 64 && has_frag && D % 32 == 0 && c.t_inter % 32 == 0) {
         // RMSNorm is deferred across the GEMMs (VCLA_DS_DEFER=0: a vcla_rmsnorm_pack launch per norm instead): o_proj / down_proj
         // store gamma * x fragment-major next to the residual stream plus per-row partial sums of squares, and the consuming
         // GEMM scales its accumulators by rstd(x): W . (gamma * x) * rstd = W . RMSNorm(x).  5 launches per layer.
@@ -764,7 +777,12 @@ static int llama_layer(vcla_ctx* ctx, hipStream_t s, const LlamaLayer& L, const 
         const bool a_def = defer && h_ready;
         const bool qkv_split = kn.ds_qkv_split && M > 32 && (int64_t)B * H >= 1024 && d >= 64 && ctx->run.splitk_ws && (size_t)2 * M * 3 * D * 4 <= SPLITK_WS_BYTES &&
                                (!a_def || ctx->run.ssq_parts == 16);
-        if (qkv_split) {
+        if (verify) {
+            RUN(gemm_ds(ctx, s, w.h, L.wqkv, L.vqkv, nullptr, 0, w.qkv, 3 * D, nullptr, M, 3 * D, D, VCLA_EPI_NONE, 0,
+                        a_def ? w.ssq : nullptr, a_def ? ctx->run.ssq_parts : 0));
+            RUN(vcla_attn_verify(w.qkv, kc, vc, ctx->rope_cos, ctx->rope_sin, w.ao, T, H, d, ctx_max, pos0, pos_dev, key_mask, scale_, dkv,
+                                 /*out_frag=*/1, ctx->run.verify_scratch, ctx->run.verify_scratch_bytes, s));
+        } else if (qkv_split) {
             RUN(gemm_ds(ctx, s, w.h, L.wqkv, L.vqkv, nullptr, 0, w.qkv, 3 * D, nullptr, M, 3 * D, D, VCLA_EPI_NONE, 0,
                         nullptr, 0, nullptr, nullptr, /*splitk=*/2, /*raw=*/true));
             const bool q8 = ctx->run.decode_step && L.vqkv.q8f && L.vqkv.s8;
@@ -802,7 +820,11 @@ static int llama_layer(vcla_ctx* ctx, hipStream_t s, const LlamaLayer& L, const 
         RUN(gemm(ctx, s, w.h, D, L.wqkv, nullptr, nullptr, 0, w.qkv, 3 * D, M, 3 * D, D, VCLA_EPI_NONE, 0, 0, 0, 0, nullptr, 0.f, &L.vqkv));
     }
     const float scale = 1.0f / sqrtf((float)d);
-    if (T == 1) {
+    if (verify) {
+        // verify rows: RoPE + KV append + causal attention over the cache, position from pos_dev
+        RUN(vcla_attn_verify(w.qkv, kc, vc, ctx->rope_cos, ctx->rope_sin, w.ao, T, H, d, ctx_max, pos0, pos_dev, key_mask, scale, dkv, 0,
+                             ctx->run.verify_scratch, ctx->run.verify_scratch_bytes, s));
+    } else if (T == 1) {
         // decode: RoPE + KV append + attention over the cache in one launch
         RUN(vcla_attn_decode_fused(w.qkv, kc, vc, ctx->rope_cos, ctx->rope_sin, w.ao, B, H, d, ctx_max, pos0, pos_dev, key_mask,
                                    ctx_max, scale, dkv, 0, s));
@@ -1086,5 +1108,109 @@ extern "C" int vcla_llama_decode_status(vcla_ctx* ctx, int B, const void* ws, si
     if (st[1]) return vcla_fail(VCLA_ERR_HIP, "decode engine: a wait timed out (site 0x%x on CU %u after %u launches); its output is invalid.  The persistent launch needs all %d CUs to itself "
                                                    "(one workgroup each, co-resident): on a shared or partitioned GPU set VCLA_ENGINE=0 to decode on the per-operator launches",
                                st[1] & 0xffffu, st[1] >> 16, st[0], EG_NCU);
+    return VCLA_OK;
+}
+
+// ------------------------------------------------------------------ prompt-lookup verify loop (B = 1)
+// Workspace: the decoder rows / logits / ids of a 16-row decode carve (R = k + 1 <= 16 rows), then the verify attention's split scratch.
+static size_t carve_verify(const vcla_ctx* ctx, int ctx_max, char* base, LlamaWs* w, void** scratch, size_t* scratch_bytes) {
+    const size_t lw = carve_llama(ctx, VCLA_LOOKUP_MAX_ROWS, 1, base, w);
+    const size_t sb = vcla_attn_verify_scratch_bytes(ctx->c.t_heads, ctx->c.t_hidden / ctx->c.t_heads, ctx_max);
+    const size_t off = (lw + 255) & ~(size_t)255;
+    if (scratch) *scratch = (base && sb) ? base + off : nullptr;
+    if (scratch_bytes) *scratch_bytes = sb;
+    return off + sb + 256;
+}
+extern "C" size_t vcla_llama_verify_workspace_bytes(const vcla_ctx* ctx, int ctx_max) {
+    if (!ctx || ctx_max <= 0 || ctx->c.t_layers <= 0) return 0;
+    return carve_verify(ctx, ctx_max, nullptr, nullptr, nullptr, nullptr);
+}
+
+// One iteration: embed the row, the decoder over its R rows, final norm + lm_head, argmax per row, the lookup bookkeeping.
+static int verify_iter_impl(vcla_ctx* ctx, hipStream_t s, const vcla_lookup_args* a, int pos0, int32_t* pos_dev, void* kv_cache, int ctx_max,
+                            const int32_t* key_mask, const LlamaWs& w) {
+    const vcla_model_cfg& c = ctx->c;
+    const int dt = c.act_dtype, D = c.t_hidden, R = a->k + 1;
+    struct Scope {
+        vcla_ctx* c;
+        explicit Scope(vcla_ctx* c_) : c(c_) { c->run.decode_step = true; c->run.verify = true; }
+        ~Scope() { c->run.decode_step = false; c->run.verify = false; }
+    } scope(ctx);
+    RUN(vcla_embed_splice(a->row, ctx->embed, nullptr, nullptr, w.x, 1, R, 0, D, c.t_vocab, dt, s));
+    for (int l = 0; l < c.t_layers; ++l)
+        RUN(llama_layer(ctx, s, ctx->llama[l], w, l, 1, R, pos0, pos_dev, kv_cache, ctx_max, key_mask, l > 0,
+                        l + 1 < c.t_layers ? ctx->llama[l + 1].ln1g : ctx->norm_g));
+    // final norm + lm_head over the R rows: decode_step_impl's tail with B = R
+    const LlamaLayer& L0 = ctx->llama[0];
+    const bool ds_layers = vcla_knobs_get().dstream && dt == VCLA_BF16 && R >= 2 && D % 32 == 0 && c.t_inter % 32 == 0 &&
+                           ((L0.vqkv.frag && L0.vo.frag && L0.vgu.frag && L0.vd.frag) || (L0.vqkv.q8f && L0.vo.q8f && L0.vgu.q8f && L0.vd.q8f));
+    if (ds_layers && (ctx->vlm.frag || ctx->vlm.q8f)) {
+        const bool defer = vcla_knobs_get().ds_defer != 0 && D % 16 == 0;
+        if (!defer) RUN(vcla_rmsnorm_pack(w.x, D, ctx->norm_g, w.h, R, D, c.t_eps, s));
+        RUN(gemm_ds(ctx, s, w.h, ctx->lm_head, ctx->vlm, nullptr, 0, w.logits, c.t_vocab, nullptr, R, c.t_vocab, D, VCLA_EPI_NONE, 1,
+                    defer ? w.ssq : nullptr, ctx->run.ssq_parts));
+    } else if (ds_layers) {
+        RUN(vcla_rmsnorm(w.x, D, ctx->norm_g, w.h, D, R, D, c.t_eps, dt, s));
+        RUN(gemm(ctx, s, w.h, D, ctx->lm_head, nullptr, nullptr, 0, w.logits, c.t_vocab, R, c.t_vocab, D, VCLA_EPI_NONE, 1, 0, 0, 0, nullptr, 0.f, &ctx->vlm));
+    } else if ((dt == VCLA_F32) ? (R <= 8) : (R == 1)) {
+        RUN(gemm(ctx, s, w.x, D, ctx->lm_head, nullptr, nullptr, 0, w.logits, c.t_vocab, R, c.t_vocab, D, VCLA_EPI_NONE, 1, 0, 0, 0, ctx->norm_g, c.t_eps, &ctx->vlm));
+    } else {
+        RUN(gemm(ctx, s, w.h, D, ctx->lm_head, nullptr, nullptr, 0, w.logits, c.t_vocab, R, c.t_vocab, D, VCLA_EPI_NONE, 1, 0, 0, 0, nullptr, 0.f, &ctx->vlm));
+    }
+    RUN(vcla_argmax(w.logits, c.t_vocab, w.ids, R, c.t_vocab, s));
+    return vcla_lookup_step(w.ids, a, pos_dev, s);
+}
+
+extern "C" int vcla_llama_verify_loop(vcla_ctx* ctx, const vcla_lookup_args* args, int pos0, int32_t* pos_dev, int n_iters, void* kv_cache,
+                                      int ctx_max, const int32_t* key_mask, void* ws, size_t ws_bytes, int use_graph, void* stream) {
+    VCLA_KNOBS_SCOPE();
+    VCLA_REQUIRE(ctx && ctx->finalized && ctx->c.t_layers > 0, VCLA_ERR_BAD_ARG, "llama_verify_loop: context not finalized, or vision-only");
+    VCLA_REQUIRE(args && pos_dev && kv_cache && ws && n_iters >= 0, VCLA_ERR_BAD_ARG, "llama_verify_loop: null pointer or n_iters < 0");
+    VCLA_REQUIRE(!ctx->c.t_kv_fp8, VCLA_ERR_BAD_ARG, "llama_verify_loop: the e4m3 K/V cache is not supported");
+    VCLA_REQUIRE(args->k >= 1 && args->k + 1 <= VCLA_LOOKUP_MAX_ROWS, VCLA_ERR_BAD_ARG, "llama_verify_loop: k=%d not in 1..%d", args->k,
+                 VCLA_LOOKUP_MAX_ROWS - 1);
+    VCLA_REQUIRE(pos0 >= 0 && ctx_max <= ctx->c.t_max_pos && pos0 + args->k + 1 <= ctx_max, VCLA_ERR_BAD_SHAPE,
+                 "llama_verify_loop: pos0=%d k=%d ctx_max=%d (max_pos %d)", pos0, args->k, ctx_max, ctx->c.t_max_pos);
+    VCLA_REQUIRE(ws_bytes >= vcla_llama_verify_workspace_bytes(ctx, ctx_max), VCLA_ERR_WORKSPACE, "llama_verify_loop: workspace %zu < %zu bytes",
+                 ws_bytes, vcla_llama_verify_workspace_bytes(ctx, ctx_max));
+    if (n_iters == 0) return VCLA_OK;
+    hipStream_t s = (hipStream_t)stream;
+    LlamaWs w;
+    void* scratch = nullptr;
+    size_t scratch_bytes = 0;
+    carve_verify(ctx, ctx_max, (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255), &w, &scratch, &scratch_bytes);
+    ctx->run.splitk_ws = w.splitk;
+    ctx->run.verify_scratch = scratch;
+    ctx->run.verify_scratch_bytes = scratch_bytes;
+    auto one_iter = [&](hipStream_t st) { return verify_iter_impl(ctx, st, args, pos0, pos_dev, kv_cache, ctx_max, key_mask, w); };
+    hipStreamCaptureStatus outer = hipStreamCaptureStatusNone;   // the caller captures this stream itself: the iterations belong in its graph
+    if (use_graph && s != nullptr && hipStreamIsCapturing(s, &outer) != hipSuccess) { (void)hipGetLastError(); outer = hipStreamCaptureStatusNone; }
+    if (!use_graph || s == nullptr || outer != hipStreamCaptureStatusNone) {
+        for (int i = 0; i < n_iters; ++i) RUN(one_iter(s));
+        return VCLA_OK;
+    }
+    auto& k = ctx->lookup_key;
+    const vcla_knobs& kn = vcla_knobs_get();
+    const bool same = ctx->lookup_exec && k.kv == kv_cache && k.mask == (const void*)key_mask && k.ws == ws && k.pos_dev == (const void*)pos_dev &&
+                      k.pos0 == pos0 && k.ctx_max == ctx_max && memcmp(&k.args, args, sizeof(*args)) == 0 && memcmp(&k.knobs, &kn, sizeof kn) == 0;
+    if (!same) {
+        if (ctx->lookup_exec) { (void)hipGraphExecDestroy(ctx->lookup_exec); ctx->lookup_exec = nullptr; }
+        hipGraph_t graph = nullptr;
+        VCLA_CHECK_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+        const int rc = one_iter(s);
+        hipError_t ce = hipStreamEndCapture(s, &graph);
+        if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
+        if (ce != hipSuccess) return vcla_fail(VCLA_ERR_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(ce));
+        hipError_t ie = hipGraphInstantiate(&ctx->lookup_exec, graph, nullptr, nullptr, 0);
+        (void)hipGraphDestroy(graph);
+        if (ie != hipSuccess) { ctx->lookup_exec = nullptr; return vcla_fail(VCLA_ERR_HIP, "hipGraphInstantiate failed: %s", hipGetErrorString(ie)); }
+        memset(&k, 0, sizeof k);
+        k.kv = kv_cache; k.mask = key_mask; k.ws = ws; k.pos_dev = pos_dev; k.pos0 = pos0; k.ctx_max = ctx_max;
+        memcpy(&k.args, args, sizeof(*args)); k.knobs = kn;
+        if (kn.macro_graph_debug) fprintf(stderr, "[vcla] lookup graph %p: capture\n", (void*)&ctx->lookup_exec);
+    } else if (kn.macro_graph_debug) {
+        fprintf(stderr, "[vcla] lookup graph %p: replay\n", (void*)&ctx->lookup_exec);
+    }
+    for (int left = n_iters; left > 0; --left) VCLA_CHECK_HIP(hipGraphLaunch(ctx->lookup_exec, s));
     return VCLA_OK;
 }

@@ -107,6 +107,34 @@ def sample_args(repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0
     return a
 
 
+LOOKUP_MAX_ROWS = 16        # VCLA_LOOKUP_MAX_ROWS: k + 1 verify rows
+LOOKUP_MAX_EOS = 4          # VCLA_LOOKUP_MAX_EOS
+LOOKUP_STATE_WORDS = 8      # VCLA_LOOKUP_STATE_WORDS: n_hist, count, done, iterations, accepted drafts, drafts of the current row
+LOOKUP_NHIST, LOOKUP_COUNT, LOOKUP_DONE, LOOKUP_ITERS, LOOKUP_ACCEPTED, LOOKUP_DRAFTS = range(6)
+
+
+class LookupArgs(C.Structure):
+    _fields_ = [
+        ("k", C.c_int), ("ngram_max", C.c_int), ("budget", C.c_int), ("n_eos", C.c_int), ("eos_ids", C.c_int * LOOKUP_MAX_EOS),
+        ("hist_cap", C.c_int), ("filler", C.c_int64),
+        ("row", C.c_void_p), ("history", C.c_void_p), ("out", C.c_void_p), ("state", C.c_void_p),
+    ]
+
+
+def lookup_args(k, ngram_max, budget, eos_ids, row, history, out, state, filler=-1):
+    """vcla_lookup_args over device tensors: row int64 [k + 1], history int64 [cap], out int64 [budget], state int32 [LOOKUP_STATE_WORDS]"""
+    eos_ids = list(eos_ids)
+    if len(eos_ids) > LOOKUP_MAX_EOS:
+        raise ValueError(f"prompt lookup takes at most {LOOKUP_MAX_EOS} eos ids (got {len(eos_ids)})")
+    a = LookupArgs()
+    a.k, a.ngram_max, a.budget, a.n_eos = int(k), int(ngram_max), int(budget), len(eos_ids)
+    for i, e in enumerate(eos_ids):
+        a.eos_ids[i] = int(e)
+    a.hist_cap, a.filler = int(history.numel()), int(filler)
+    a.row, a.history, a.out, a.state = ptr(row), ptr(history), ptr(out), ptr(state)
+    return a
+
+
 # every symbol include/visualcla_hip.h declares: name -> (restype, argtypes)
 _vp, _i, _i64, _f, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
 SYMBOLS = {
@@ -146,6 +174,11 @@ SYMBOLS = {
     "vcla_llama_decode_loop": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _sz, _i, _vp]),
     "vcla_llama_decode_status": (_i, [_vp, _i, _vp, _sz, _vp]),
     "vcla_llama_decode_loop_sampled": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _sz, _i, C.POINTER(SampleArgs), _i, _vp]),
+    "vcla_attn_verify_scratch_bytes": (_sz, [_i, _i, _i]),
+    "vcla_attn_verify": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _f, _i, _i, _vp, _sz, _vp]),
+    "vcla_lookup_step": (_i, [_vp, C.POINTER(LookupArgs), _vp, _vp]),
+    "vcla_llama_verify_workspace_bytes": (_sz, [_vp, _i]),
+    "vcla_llama_verify_loop": (_i, [_vp, C.POINTER(LookupArgs), _i, _vp, _i, _vp, _i, _vp, _vp, _sz, _i, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

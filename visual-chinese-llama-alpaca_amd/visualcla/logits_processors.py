@@ -30,7 +30,6 @@ _REFUSED = (
     ("num_beam_groups", lambda v: v is not None and v > 1, "group beam search"),
     ("diversity_penalty", lambda v: v is not None and v != 0.0, "group beam search"),
     ("dola_layers", lambda v: v is not None, "DoLa decoding"),
-    ("prompt_lookup_num_tokens", lambda v: v is not None, "prompt-lookup decoding"),
     ("constraints", lambda v: v is not None, "constrained beam search"),
     ("force_words_ids", lambda v: v is not None, "constrained beam search"),
     ("forced_decoder_ids", lambda v: v is not None, "forced decoder ids"),

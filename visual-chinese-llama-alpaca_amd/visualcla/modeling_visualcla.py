@@ -746,11 +746,16 @@ class VisualCLAModel:
         if nb == 1 and (gc.num_return_sequences or 1) != 1 and not gc.do_sample:
             # HF's wording (generation/configuration_utils.py validate): several returned sequences need beams or sampling
             raise ValueError(f"Greedy methods without beam search do not support `num_return_sequences` different than 1 (got {gc.num_return_sequences}).")
+        self._refuse_lookup_conflicts(gc, logits_processor, stopping_criteria, prefix_allowed_tokens_fn, device_sampling)
+        if getattr(gc, "prompt_lookup_num_tokens", None) is not None and getattr(self, "_kv_fp8", False):
+            raise ValueError("prompt_lookup_num_tokens cannot be combined with the e4m3 K/V cache (enable_fp8_decode(kv_cache=True))")
         # prefix_allowed_tokens_fn: the reference forwards it to HF generate (modeling_visualcla.py:382-391), which turns it into a processor placed
         # among the configured ones (it sees the NEW tokens only, as every processor does when HF is driven by inputs_embeds).  Host-driven step path.
         t = self.config.text_config
         input_ids = self._prepare_ids(input_ids, pixel_values)
         B = input_ids.shape[0]
+        if getattr(gc, "prompt_lookup_num_tokens", None) is not None and B != 1:
+            raise ValueError(f"prompt_lookup_num_tokens is implemented for batch size 1 (got batch size {B}), as HF's assisted generation")
         if use_graph is None:
             use_graph = os.environ.get("VCLA_DECODE_GRAPH", "1") != "0"
         # hipGraph capture (decode loop; vision stack and prefill inside the engine) is illegal on the legacy default stream: the
@@ -810,6 +815,109 @@ class VisualCLAModel:
                            num_return_sequences=int(gc.num_return_sequences or 1), processors=procs,
                            stopping_criteria=list(stopping_criteria) if stopping_criteria else ())
 
+    # ------------------------------------------------------------------ prompt-lookup decoding
+    @staticmethod
+    def _refuse_lookup_conflicts(gc, logits_processor, stopping_criteria, prefix_fn, device_sampling) -> None:
+        """prompt_lookup_num_tokens runs greedy decoding at B = 1 without processors: every other setting it meets is refused by name"""
+        k = getattr(gc, "prompt_lookup_num_tokens", None)
+        if k is None:
+            return
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= _lib.LOOKUP_MAX_ROWS - 1:
+            raise ValueError(f"prompt_lookup_num_tokens must be an integer in 1..{_lib.LOOKUP_MAX_ROWS - 1} (got {k!r})")
+        ng = getattr(gc, "max_matching_ngram_size", None)
+        if ng is not None and (isinstance(ng, bool) or not isinstance(ng, int) or ng < 1):
+            raise ValueError(f"max_matching_ngram_size must be a positive integer (got {ng!r})")
+        from .logits_processors import min_token_floor
+        bad = []
+        if gc.do_sample:
+            bad.append("do_sample=True")
+        if int(gc.num_beams or 1) > 1:
+            bad.append(f"num_beams={gc.num_beams}")
+        if int(gc.num_return_sequences or 1) != 1:
+            bad.append(f"num_return_sequences={gc.num_return_sequences}")
+        if gc.repetition_penalty is not None and gc.repetition_penalty != 1.0:
+            bad.append(f"repetition_penalty={gc.repetition_penalty}")
+        if gc.no_repeat_ngram_size:
+            bad.append(f"no_repeat_ngram_size={gc.no_repeat_ngram_size}")
+        if getattr(gc, "min_new_tokens", None):
+            bad.append(f"min_new_tokens={gc.min_new_tokens}")
+        if getattr(gc, "min_length", None) and min_token_floor(gc, 0) > 0:
+            bad.append(f"min_length={gc.min_length}")
+        if logits_processor:
+            bad.append("logits_processor")
+        if stopping_criteria:
+            bad.append("stopping_criteria")
+        if prefix_fn is not None:
+            bad.append("prefix_allowed_tokens_fn")
+        if getattr(gc, "max_time", None) is not None:
+            bad.append("max_time")
+        if device_sampling:
+            bad.append("device_sampling=True")
+        if bad:
+            raise ValueError("prompt_lookup_num_tokens (prompt-lookup decoding) is implemented for plain greedy decoding only; it cannot be combined with "
+                             + ", ".join(bad))
+
+    def _lookup_k(self, gc, T: int, n_new: int, max_pos: int) -> int:
+        """drafts per verify pass: prompt_lookup_num_tokens, shrunk so that T + n_new + k fits max_position_embeddings; 0 = plain greedy (the
+        same ids: the field only changes how many passes over the weights produce them)"""
+        k = getattr(gc, "prompt_lookup_num_tokens", None)
+        if k is None:
+            return 0
+        if len(self._eos_list(gc)) > _lib.LOOKUP_MAX_EOS:
+            raise ValueError(f"prompt_lookup_num_tokens takes at most {_lib.LOOKUP_MAX_EOS} eos_token_id values")
+        k = min(int(k), max_pos - T - n_new)
+        return k if k >= 1 else 0
+
+    def _lookup_generate(self, gc, input_ids, T, n_new, ctx_max, cache, key_mask, logits, eos, k, use_graph, persistent):
+        """Greedy decoding with prompt-lookup drafts (HF generate(prompt_lookup_num_tokens=k): generation/utils.py _assisted_decoding with
+        candidate_generator.py PromptLookupCandidateGenerator).  Each verify iteration feeds the last token and k drafts through the decoder in one
+        pass (vcla_llama_verify_loop), accepts the leading drafts equal to the argmax of the row before them and emits those plus one bonus token:
+        the returned ids are exactly plain greedy's.
+
+        The drafts are looked up in the prompt's TEXT ids (the image placeholder ids removed) followed by the generated ids.  HF driven by
+        inputs_embeds, as the reference drives it, looks up in the generated ids only; the difference changes which drafts are proposed, never
+        which tokens are returned.  model.last_lookup_stats: verify iterations and accepted drafts of the call."""
+        lib = _lib.load()
+        dev = self._device
+        first = int(_lib.argmax(logits)[0])
+        img_id = getattr(self.tokenizer, "img_token_id", None) if self.tokenizer is not None else None
+        txt = input_ids[0]
+        if img_id is not None:
+            txt = txt[txt != int(img_id)]
+        n_txt = int(txt.numel())
+        ngram = int(getattr(gc, "max_matching_ngram_size", None) or 2)
+
+        def buf(name, shape, dtype):
+            return self._typed_buf(name, shape, dtype) if persistent else torch.empty(*shape, dtype=dtype, device=dev)
+        hist = buf("lk_hist", (n_txt + n_new,), torch.int64)
+        out = buf("lk_out", (n_new,), torch.int64)
+        row = buf("lk_row", (k + 1,), torch.int64)
+        state = buf("lk_state", (_lib.LOOKUP_STATE_WORDS,), torch.int32)
+        hist[:n_txt].copy_(txt)
+        hist[n_txt] = first
+        out[0] = first
+        done = n_new == 1 or first in eos
+        init = [0] * _lib.LOOKUP_STATE_WORDS
+        init[_lib.LOOKUP_NHIST], init[_lib.LOOKUP_COUNT], init[_lib.LOOKUP_DONE] = n_txt + 1, 1, int(done)
+        state.copy_(torch.tensor(init, dtype=torch.int32))
+        self._pos_dev.zero_()                       # the row's first token sits at position T + *pos_dev
+        args = _lib.lookup_args(k, ngram, n_new, eos, row, hist, out, state)
+        ws = self._buf("lookup", lib.vcla_llama_verify_workspace_bytes(self._ctx, ctx_max))
+        stream = _lib.stream_ptr()
+        _lib.check(lib.vcla_lookup_step(None, C.byref(args), self._pos_dev.data_ptr(), stream))      # the first row
+        count, chunk = 1, 8
+        st = init
+        while not done:
+            # every iteration emits at least one token until done; replays after done change nothing
+            n_it = min(chunk, n_new - count)
+            _lib.check(lib.vcla_llama_verify_loop(self._ctx, C.byref(args), T, self._pos_dev.data_ptr(), n_it, cache.kv.data_ptr(), ctx_max,
+                                                  _lib.ptr(key_mask), ws.data_ptr(), ws.numel(), int(use_graph), stream))
+            st = state.tolist()                     # one synchronisation per chunk
+            count, done = st[_lib.LOOKUP_COUNT], bool(st[_lib.LOOKUP_DONE]) or st[_lib.LOOKUP_COUNT] >= n_new
+        # (the verify passes never run the persistent B = 1 decode step, so there is no engine wait status to check here)
+        self.last_lookup_stats = {"k": k, "iterations": int(st[_lib.LOOKUP_ITERS]), "accepted": int(st[_lib.LOOKUP_ACCEPTED]), "tokens": int(count)}
+        return out[:count].view(1, count).clone()
+
     def _generate_on_stream(self, gc, input_ids, pixel_values, attention_mask, logits_processor, stopping_criteria, use_graph, device_sampling,
                             prefix_fn=None):
         lib = _lib.load()
@@ -834,7 +942,8 @@ class VisualCLAModel:
         n_new = min(new_token_budget(gc, T), max_pos - T)         # max_new_tokens, else max_length less the prompt, else 20 (HF's rules for inputs_embeds)
         if n_new <= 0:
             raise ValueError(f"prompt of {T} tokens leaves no room under max_position_embeddings={max_pos}")
-        ctx_max = min(max_pos, (T + n_new + 63) // 64 * 64)
+        lookup_k = self._lookup_k(gc, T, n_new, max_pos)
+        ctx_max = min(max_pos, (T + n_new + lookup_k + 63) // 64 * 64)    # the rows of the last verify pass stay inside the cache
         eos = self._eos_list(gc)
         if int(gc.num_beams or 1) > 1:
             return self._beam_generate(gc, embeds, am, T, n_new, ctx_max, eos, logits_processor, stopping_criteria, prefix_fn)
@@ -859,6 +968,11 @@ class VisualCLAModel:
             raise ValueError("device_sampling=True but the generation config needs HF's processors on the host-driven path "
                              "(custom logits_processor, or top_k outside [1, %d])" % _lib.SAMPLE_MAX_TOP_K)
         fast = not criteria and (plain_greedy or samp_kw is not None)
+        if lookup_k:
+            if procs:       # a processor _refuse_lookup_conflicts did not name: refuse rather than drop it
+                raise ValueError("prompt_lookup_num_tokens runs plain greedy decoding; it cannot be combined with "
+                                 + ", ".join(type(p).__name__ for p in procs))
+            return self._lookup_generate(gc, input_ids, T, n_new, ctx_max, cache, key_mask, logits, eos, lookup_k, use_graph, persistent)
         if fast:
             # ---- device-resident loop: argmax, or the on-device sampler, feeds the next step
             out = self._typed_buf("gen_out", (n_new, B), torch.int64) if persistent else torch.empty(n_new, B, dtype=torch.int64, device=self._device)
