@@ -13,6 +13,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <new>
 #include <string>
 #include <unordered_map>
@@ -109,6 +110,44 @@ struct LlamaLayer {
     WVar vqkv, vo, vgu, vd;
 };
 
+// Captured graphs of one entry point.  A slot's key (key_bytes) is a struct of everything its launches bake in -- pointers, shapes,
+// arguments; memset before it is filled, as keys compare bytewise -- followed by the switch snapshot that chose them.
+struct GraphCache {
+    struct Slot {
+        std::string key;
+        hipGraphExec_t exec = nullptr;
+        unsigned long long used = 0;   // last-use tick; 0: empty
+    };
+    std::vector<Slot> slots;
+    unsigned long long tick = 0;
+    std::string seen;                  // run_macro: the key of the previous eager call (empty: none yet)
+    explicit GraphCache(int n) : slots(n) {}
+    int find(const std::string& key) {   // the slot holding key (a use), or -1
+        for (int i = 0; i < (int)slots.size(); ++i) {
+            if (!slots[i].exec || slots[i].key != key) continue;
+            slots[i].used = ++tick;
+            return i;
+        }
+        return -1;
+    }
+    void put(const std::string& key, hipGraphExec_t exec) {   // into the first empty slot, else the least recently used one
+        Slot& victim = *std::min_element(slots.begin(), slots.end(), [](const Slot& a, const Slot& b) { return a.used < b.used; });
+        if (victim.exec) (void)hipGraphExecDestroy(victim.exec);   // no device synchronise: it would wait for the launches issued before the capture
+        victim = Slot{key, exec, ++tick};
+    }
+    void clear() {   // behind a device synchronise
+        for (Slot& sl : slots)
+            if (sl.exec) (void)hipGraphExecDestroy(sl.exec);
+        *this = GraphCache((int)slots.size());
+    }
+};
+template <typename K>
+static std::string key_bytes(const K& k) {
+    static_assert(std::is_trivially_copyable_v<K>, "graph keys are compared bytewise");
+    const vcla_knobs& kn = vcla_knobs_get();
+    return std::string((const char*)&k, sizeof k).append((const char*)&kn, sizeof kn);
+}
+
 struct vcla_ctx {
     vcla_model_cfg c;
     std::unordered_map<std::string, TensorRef> tensors;
@@ -126,6 +165,7 @@ struct vcla_ctx {
     const float* proj_b = nullptr;
     const void* embed = nullptr;
     std::vector<LlamaLayer> llama;
+    bool twins_complete = false;   // every LLaMA layer has all four bf16 ".f" twins or all four fp8 ".q8f" copies (the streaming decode layers)
     const float* norm_g = nullptr;
     const void* lm_head = nullptr;
     WVar vlm;
@@ -139,7 +179,7 @@ struct vcla_ctx {
     // per-call state of the macro entry points (one thread drives a context at a time): the workspace carve of the
     // running call and what the last streaming GEMM left behind.  Kept here, not in thread-local globals, so that nothing
     // leaks between contexts or into the public vcla_gemm entry point.
-    struct {
+    struct RunState {
         void* splitk_ws = nullptr;     // fp32 split-K scratch of the running entry point's workspace
         bool decode_step = false;      // inside decode_step_impl: the fp8 weight copies (if loaded) may be used
         void* q8_ws = nullptr;         // fp8 activation staging of the running prefill (t_fp8_mfma), else NULL
@@ -149,39 +189,18 @@ struct vcla_ctx {
         void* verify_scratch = nullptr;
         size_t verify_scratch_bytes = 0;
     } run;
-    // cached graphs of the vision stack and of the prefill (fixed launch sequences per shape: ~250 / ~290 launches that are host-bound
-    // at B = 1).  Keyed on every pointer and shape the captured launches bake in and on the switch snapshot that chose them; see run_macro.
-    struct MacroGraph {
-        static constexpr int kSlots = 2;        // two shapes in rotation (e.g. forward(all_logits) and generate()'s prefill, or two batch sizes) both stay cached
-        struct Key {
-            const void* p[8];
-            vcla_knobs knobs;
-        };
-        hipGraphExec_t exec[kSlots] = {};
-        Key key[kSlots] = {};                   // of the captured graphs
-        unsigned long long used[kSlots] = {};   // last-use tick: the older slot is the one replaced
-        unsigned long long tick = 0;
-        Key seen = {};                          // of the previous eager call
-        int has_seen = 0;
-    } vision_graph, prefill_graph;
-    // cached decode graph: one decode step
-    hipGraphExec_t graph_exec = nullptr;
-    struct {
-        const void *ids, *kv, *mask, *ws, *out;
-        int B, pos0, ctx_max, step_base;
-        const void* pos_dev;
-        int has_samp, n_hist0;
-        vcla_sample_args samp;
-        vcla_knobs knobs;
-    } graph_key = {};
-    // cached prompt-lookup graph: one verify iteration (its own slot, so that a plain generate() afterwards still replays graph_exec)
-    hipGraphExec_t lookup_exec = nullptr;
-    struct {
-        const void *kv, *mask, *ws, *pos_dev;
-        int pos0, ctx_max;
-        vcla_lookup_args args;
-        vcla_knobs knobs;
-    } lookup_key = {};
+    // cached graphs of the vision stack and of the prefill (~250 / ~290 launches, host-bound at B = 1; run_macro), two shapes in rotation
+    // each (e.g. forward(all_logits) and generate()'s prefill, or two batch sizes); of one decode step and of one verify iteration
+    // (run_steps), apart so that a plain generate() after a prompt-lookup one still replays its decode graph
+    GraphCache vision_graph{2}, prefill_graph{2}, decode_graph{1}, verify_graph{1};
+};
+
+// ctx->run as it was when the scope opened is restored when it closes
+struct RunScope {
+    vcla_ctx* ctx;
+    const vcla_ctx::RunState saved;
+    explicit RunScope(vcla_ctx* c) : ctx(c), saved(c->run) {}
+    ~RunScope() { ctx->run = saved; }
 };
 
 static inline int pad_to(int x, int m) { return (x + m - 1) / m * m; }
@@ -226,17 +245,12 @@ extern "C" int vcla_ctx_create(const vcla_model_cfg* cfg, vcla_ctx** out) {
 static void drop_graphs(vcla_ctx* ctx) {
     // An exec may still be executing (its last hipGraphLaunch is asynchronous) and HIP does not promise deferred destruction on every ROCm
     // version: drain the device first.  Only when there is something to destroy -- registering the tensors of a fresh context costs nothing.
-    bool any = ctx->graph_exec != nullptr || ctx->lookup_exec != nullptr;
-    for (const vcla_ctx::MacroGraph* g : {&ctx->vision_graph, &ctx->prefill_graph})
-        for (int i = 0; i < vcla_ctx::MacroGraph::kSlots; ++i) any = any || g->exec[i];
+    GraphCache* const caches[] = {&ctx->vision_graph, &ctx->prefill_graph, &ctx->decode_graph, &ctx->verify_graph};
+    bool any = false;
+    for (const GraphCache* g : caches)
+        for (const GraphCache::Slot& sl : g->slots) any = any || sl.exec;
     if (any && hipDeviceSynchronize() != hipSuccess) (void)hipGetLastError();
-    if (ctx->graph_exec) { (void)hipGraphExecDestroy(ctx->graph_exec); ctx->graph_exec = nullptr; }
-    if (ctx->lookup_exec) { (void)hipGraphExecDestroy(ctx->lookup_exec); ctx->lookup_exec = nullptr; }
-    for (vcla_ctx::MacroGraph* g : {&ctx->vision_graph, &ctx->prefill_graph}) {
-        for (int i = 0; i < vcla_ctx::MacroGraph::kSlots; ++i)
-            if (g->exec[i]) { (void)hipGraphExecDestroy(g->exec[i]); g->exec[i] = nullptr; }
-        g->has_seen = 0;
-    }
+    for (GraphCache* g : caches) g->clear();
 }
 
 extern "C" void vcla_ctx_destroy(vcla_ctx* ctx) {
@@ -377,6 +391,10 @@ extern "C" int vcla_ctx_finalize(vcla_ctx* ctx) {
         GET_WF(L.vgu, p + "wgu", 2 * c.t_inter, c.t_hidden);
         GET_WF(L.vd, p + "wd", c.t_hidden, c.t_inter);
     }
+    // all layers or none: each streaming layer leaves w.h / w.ssq in the layout the next one and the final norm + lm_head read
+    ctx->twins_complete = std::all_of(ctx->llama.begin(), ctx->llama.end(), [](const LlamaLayer& L) {
+        return (L.vqkv.frag && L.vo.frag && L.vgu.frag && L.vd.frag) || (L.vqkv.q8f && L.vo.q8f && L.vgu.q8f && L.vd.q8f);
+    });
     GET_F(ctx->norm_g, "llama.norm.g", c.t_hidden);
     GET_W(ctx->lm_head, "llama.lm_head", c.t_vocab, c.t_hidden);
     GET_WF(ctx->vlm, "llama.lm_head", c.t_vocab, c.t_hidden);
@@ -403,6 +421,8 @@ extern "C" int vcla_ctx_finalize(vcla_ctx* ctx) {
 }
 
 // ------------------------------------------------------------------ workspace
+static inline char* align256(const void* p) { return (char*)(((uintptr_t)p + 255) & ~(uintptr_t)255); }
+
 struct Bump {
     char* base;
     size_t off, cap;
@@ -569,71 +589,91 @@ static int tap_copy(void* tap, size_t index, const void* src, size_t bytes, hipS
     return VCLA_OK;
 }
 
-// ------------------------------------------------------------------ macro graphs (vision stack, prefill)
-// run(stream) issues the launch sequence.  Replay when `key` matches the captured graph; capture when it matches the previous eager
-// call; else run eagerly and remember the key.  Capture is illegal on the legacy default stream (s == 0): eager there.
-template <typename F>
-static int run_macro(vcla_ctx::MacroGraph& g, const void* const (&ptrs)[8], hipStream_t s, F&& run) {
-    const vcla_knobs& kn = vcla_knobs_get();
-    if (!kn.macro_graph || s == nullptr) return run(s);
-    // The caller is capturing on this stream itself (torch.cuda.graph, or its own hipGraph around this entry point): the launches
-    // belong in ITS graph -- replaying ours or opening a nested capture would both be wrong.
+// ------------------------------------------------------------------ cached graphs
+// Whether a graph may be captured or replayed on s: not on the legacy default stream (capture is illegal there), nor while the caller
+// captures s itself (torch.cuda.graph, or its own hipGraph around this entry point) -- the launches then belong in ITS graph, and
+// replaying ours or opening a nested capture would both be wrong.  When the query fails, eager is right either way.
+static bool graph_ok(hipStream_t s) {
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cap) != hipSuccess) { (void)hipGetLastError(); return run(s); }
-    if (cap != hipStreamCaptureStatusNone) return run(s);
+    if (s == nullptr) return false;
+    if (hipStreamIsCapturing(s, &cap) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return cap == hipStreamCaptureStatusNone;
+}
+
+// The launches of run(s), recorded into a graph and instantiated.  exec is nullptr when the step `call` failed with e ("capture": the
+// recorded launches, whose own error code is then rc, or closing the capture).
+struct Captured { hipGraphExec_t exec; int rc; const char* call; hipError_t e; };
+template <typename F>
+static Captured capture_graph(hipStream_t s, F&& run) {
+    Captured c = {nullptr, VCLA_OK, "hipStreamBeginCapture", hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal)};
+    if (c.e != hipSuccess) return c;
+    hipGraph_t graph = nullptr;
+    c.rc = run(s);
+    c.call = "capture";
+    c.e = hipStreamEndCapture(s, &graph);
+    if (c.rc || c.e != hipSuccess) {
+        if (graph) (void)hipGraphDestroy(graph);
+        return c;
+    }
+    hipGraphExec_t exec = nullptr;
+    c = {nullptr, VCLA_OK, "hipGraphInstantiate", hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0)};
+    (void)hipGraphDestroy(graph);
+    if (c.e == hipSuccess) c.exec = exec;
+    return c;
+}
+
+// Macro graphs (vision stack, prefill): run(stream) issues the launch sequence, replayed from g when `key` matches a captured graph.
+template <typename K, typename F>
+static int run_macro(GraphCache& g, const K& key_fields, hipStream_t s, F&& run) {
+    const vcla_knobs& kn = vcla_knobs_get();
+    if (!kn.macro_graph || !graph_ok(s)) return run(s);
     const int dbg = kn.macro_graph_debug;
-    vcla_ctx::MacroGraph::Key key;
-    memset(&key, 0, sizeof key);
-    memcpy(key.p, ptrs, sizeof key.p);
-    key.knobs = kn;
-    constexpr int NS = vcla_ctx::MacroGraph::kSlots;
-    for (int i = 0; i < NS; ++i) {
-        if (g.exec[i] && memcmp(&g.key[i], &key, sizeof key) == 0) {
-            VCLA_CHECK_HIP(hipGraphLaunch(g.exec[i], s));
-            g.used[i] = ++g.tick;
-            if (dbg) fprintf(stderr, "[vcla] macro graph %p: replay (slot %d)\n", (void*)&g, i);
-            return VCLA_OK;
-        }
+    const std::string key = key_bytes(key_fields);
+    const int slot = g.find(key);
+    if (slot >= 0) {
+        VCLA_CHECK_HIP(hipGraphLaunch(g.slots[slot].exec, s));
+        if (dbg) fprintf(stderr, "[vcla] macro graph %p: replay (slot %d)\n", (void*)&g, slot);
+        return VCLA_OK;
     }
     if (dbg) fprintf(stderr, "[vcla] macro graph %p: eager call (no captured graph has this key)\n", (void*)&g);
     // not a captured key: this call runs eagerly (which also leaves every per-device function attribute set); the graph is
     // captured behind it -- recorded, not executed -- when the key is the very first one or repeats the previous eager call's, so a
     // caller whose buffers move on every call never pays for captures it cannot reuse
-    const bool repeat = g.has_seen && memcmp(&g.seen, &key, sizeof key) == 0;
-    const bool first = !g.has_seen;
+    const bool capture = g.seen.empty() || g.seen == key;
     g.seen = key;
-    g.has_seen = 1;
     const int rc_eager = run(s);
-    if (rc_eager || !(repeat || first)) return rc_eager;
+    if (rc_eager || !capture) return rc_eager;
     // From here on the call has SUCCEEDED (the eager launches are issued): a capture that cannot be taken or instantiated only means
     // "no cached graph" -- the next call runs eagerly again.
-    auto no_graph = [&](const char* what, hipError_t e) {
-        if (dbg) fprintf(stderr, "[vcla] macro graph %p: %s failed (%s), staying eager\n", (void*)&g, what, hipGetErrorString(e));
+    const Captured c = capture_graph(s, run);
+    if (!c.exec) {
+        if (dbg) fprintf(stderr, "[vcla] macro graph %p: %s failed (%s), staying eager\n", (void*)&g, c.call, hipGetErrorString(c.e));
         (void)hipGetLastError();
         return VCLA_OK;
-    };
-    hipGraph_t graph = nullptr;
-    hipError_t e = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
-    if (e != hipSuccess) return no_graph("hipStreamBeginCapture", e);
-    const int rc = run(s);
-    e = hipStreamEndCapture(s, &graph);
-    if (rc || e != hipSuccess) {
-        if (graph) (void)hipGraphDestroy(graph);
-        return no_graph("capture", e);
     }
-    hipGraphExec_t exec = nullptr;
-    e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(graph);
-    if (e != hipSuccess) return no_graph("hipGraphInstantiate", e);
-    int victim = 0;
-    for (int i = 0; i < NS; ++i) {
-        if (!g.exec[i]) { victim = i; break; }
-        if (g.used[i] < g.used[victim]) victim = i;
+    g.put(key, c.exec);
+    return VCLA_OK;
+}
+
+// Step graphs (the decode and verify loops).  step(stream) issues the launches of one step: captured when `key` is new, then replayed
+// n times.  `name` labels the debug lines.
+template <typename K, typename F>
+static int run_steps(GraphCache& g, const char* name, const K& key_fields, int use_graph, int n, hipStream_t s, F&& step) {
+    if (!use_graph || !graph_ok(s)) {
+        for (int i = 0; i < n; ++i) RUN(step(s));
+        return VCLA_OK;
     }
-    if (g.exec[victim]) (void)hipGraphExecDestroy(g.exec[victim]);
-    g.exec[victim] = exec;
-    g.used[victim] = ++g.tick;
-    g.key[victim] = key;
+    const std::string key = key_bytes(key_fields);
+    const int slot = g.find(key);
+    hipGraphExec_t exec = slot >= 0 ? g.slots[slot].exec : nullptr;
+    if (!exec) {
+        const Captured c = capture_graph(s, step);
+        if (c.rc) return c.rc;
+        if (!c.exec) return vcla_fail(VCLA_ERR_HIP, "%s failed: %s", c.call, hipGetErrorString(c.e));
+        g.put(key, exec = c.exec);
+    }
+    if (vcla_knobs_get().macro_graph_debug) fprintf(stderr, "[vcla] %s graph %p: %s\n", name, (void*)&g, slot >= 0 ? "replay" : "capture");
+    for (int left = n; left > 0; --left) VCLA_CHECK_HIP(hipGraphLaunch(exec, s));
     return VCLA_OK;
 }
 
@@ -651,7 +691,9 @@ extern "C" int vcla_vision_forward(vcla_ctx* ctx, const void* pixel_values, void
                  ws_bytes, vcla_vision_workspace_bytes(ctx, B));
     hipStream_t s = (hipStream_t)stream;
     if (vit_tap || res_tap) return vision_forward_impl(ctx, pixel_values, image_embeds, B, ws, vit_tap, res_tap, s);   // parity runs: eager
-    const void* const key[8] = {pixel_values, image_embeds, ws, (const void*)(intptr_t)B, (const void*)(intptr_t)ctx->c.v_image, nullptr, nullptr, nullptr};
+    struct { const void *pixel_values, *image_embeds, *ws; int B, v_image; } key;
+    memset(&key, 0, sizeof key);
+    key.pixel_values = pixel_values; key.image_embeds = image_embeds; key.ws = ws; key.B = B; key.v_image = ctx->c.v_image;
     return run_macro(ctx->vision_graph, key, s, [&](hipStream_t st) { return vision_forward_impl(ctx, pixel_values, image_embeds, B, ws, nullptr, nullptr, st); });
 }
 
@@ -662,7 +704,7 @@ static int vision_forward_impl(vcla_ctx* ctx, const void* pixel_values, void* im
     const size_t e = esz(ctx);
     const int g = c.v_image / c.v_patch, np = g * g, N = np + 1, D = c.v_hidden, H = c.v_heads, d = D / H;
     VisionWs w;
-    carve_vision(ctx, B, (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255), &w);
+    carve_vision(ctx, B, align256(ws), &w);
     ctx->run.splitk_ws = w.splitk;
     const int M = B * N;
 
@@ -735,6 +777,17 @@ static int vision_forward_impl(vcla_ctx* ctx, const void* pixel_values, void* im
 }
 
 // ------------------------------------------------------------------ LLaMA decoder
+// M rows go to the GEMV kernel, which applies the RMSNorm in its prologue (norm_gamma): must mirror vcla_gemm's kernel choice.
+static bool gemv_norm(int dt, int M) { return (dt == VCLA_F32) ? (M <= 8) : (M == 1); }
+
+// 2 <= M <= 64 rows of a decode step (T = 1) or a verify iteration run the streaming decode GEMMs (gemm_stream.hip).  The final norm +
+// lm_head asks the same question: it consumes w.h / w.ssq in the layout these layers leave behind.
+static bool stream_layers(const vcla_ctx* ctx, int M, int T) {
+    const vcla_model_cfg& c = ctx->c;
+    return vcla_knobs_get().dstream && ctx->run.decode_step && (T == 1 || ctx->run.verify) && c.act_dtype == VCLA_BF16 && M >= 2 && M <= 64 &&
+           ctx->twins_complete && c.t_hidden % 32 == 0 && c.t_inter % 32 == 0;
+}
+
 // One decoder layer over M = B*T rows held in ws.x (updated in place).
 static int llama_layer(vcla_ctx* ctx, hipStream_t s, const LlamaLayer& L, const LlamaWs& w, int l, int B, int T, int pos0,
                        const int32_t* pos_dev, void* kv_cache, int ctx_max, const int32_t* key_mask, bool h_ready = false,
@@ -753,12 +806,11 @@ static int llama_layer(vcla_ctx* ctx, hipStream_t s, const LlamaLayer& L, const 
     // the SwiGLU epilogue stores the activations that way; the residual stream w.x stays row-major.  7 launches per layer,
     // no split-K partials.
     const vcla_knobs& kn = vcla_knobs_get();
-    const bool has_frag = (L.vqkv.frag && L.vo.frag && L.vgu.frag && L.vd.frag) || (L.vqkv.q8f && L.vo.q8f && L.vgu.q8f && L.vd.q8f);
-    // Decode steps only (ctx->run.decode_step): the branch leaves w.h fragment-major and un-normalised, which decode_step_impl's
+    // Decode steps only (ctx->run.decode_step): the branch leaves w.h fragment-major and un-normalised, which decoder_rows'
     // final norm + lm_head expect and vcla_llama_prefill's all_logits tail (row-major w.h) does not -- a single-token
     // forward(input_ids[B, 1], past_key_values=cache) goes through the panel kernels below.
     const bool verify = ctx->run.verify;   // B = 1, T = k + 1 verify rows at pos0 + *pos_dev (vcla_llama_verify_loop)
-    if (kn.dstream && ctx->run.decode_step && (T == 1 || verify) && dt == VCLA_BF16 && M >= 2 && M <= 64 && has_frag && D % 32 == 0 && c.t_inter % 32 == 0) {
+    if (stream_layers(ctx, M, T)) {
         // RMSNorm is deferred across the GEMMs (VCLA_DS_DEFER=0: a vcla_rmsnorm_pack launch per norm instead): o_proj / down_proj
         // store gamma * x fragment-major next to the residual stream plus per-row partial sums of squares, and the consuming
         // GEMM scales its accumulators by rstd(x): W . (gamma * x) * rstd = W . RMSNorm(x).  5 launches per layer.
@@ -809,7 +861,7 @@ static int llama_layer(vcla_ctx* ctx, hipStream_t s, const LlamaLayer& L, const 
         return VCLA_OK;
     }
     // M <= 8 rows (decode): the GEMV kernel applies RMSNorm in its prologue -- no norm launch, no normalised copy.
-    const bool fused = (dt == VCLA_F32) ? (M <= 8) : (M == 1);  // must mirror vcla_gemm's kernel choice
+    const bool fused = gemv_norm(dt, M);
     // Otherwise the norms ride on the producing GEMM (post_norm_*: fused into the split-K reduction for M <= 128, a plain
     // vcla_rmsnorm launch behind the big tiles): o_proj emits post_attention_layernorm(x) and down_proj emits the NEXT
     // layer's input_layernorm(x) -- or the final norm -- into w.h.  `h_ready`: w.h already holds this layer's ln1(x).
@@ -860,6 +912,33 @@ static int llama_layer(vcla_ctx* ctx, hipStream_t s, const LlamaLayer& L, const 
     return VCLA_OK;
 }
 
+// The decoder over the B x T rows in w.x of a decode step (T = 1) or a verify iteration (B = 1), then the final norm + lm_head into lg
+// [B * T, vocab].  The norms ride on the producing GEMMs; the last layer's emits the final norm.
+static int decoder_rows(vcla_ctx* ctx, hipStream_t s, const LlamaWs& w, int B, int T, int pos0, int32_t* pos_dev, void* kv_cache,
+                        int ctx_max, const int32_t* key_mask, float* lg) {
+    const vcla_model_cfg& c = ctx->c;
+    const int dt = c.act_dtype, D = c.t_hidden, M = B * T;
+    for (int l = 0; l < c.t_layers; ++l)
+        RUN(llama_layer(ctx, s, ctx->llama[l], w, l, B, T, pos0, pos_dev, kv_cache, ctx_max, key_mask, l > 0,
+                        l + 1 < c.t_layers ? ctx->llama[l + 1].ln1g : ctx->norm_g));
+    const bool ds_layers = stream_layers(ctx, M, T);
+    if (ds_layers && (ctx->vlm.frag || ctx->vlm.q8f)) {
+        // streaming layers leave the residual stream in w.x: final norm -> fragment-major, lm_head streamed the same way
+        const bool defer = vcla_knobs_get().ds_defer != 0 && D % 16 == 0;     // the last down_proj left gamma_final * x and its row statistics in w.h / w.ssq
+        if (!defer) RUN(vcla_rmsnorm_pack(w.x, D, ctx->norm_g, w.h, M, D, c.t_eps, s));
+        RUN(gemm_ds(ctx, s, w.h, ctx->lm_head, ctx->vlm, nullptr, 0, lg, c.t_vocab, nullptr, M, c.t_vocab, D, VCLA_EPI_NONE, 1,
+                    defer ? w.ssq : nullptr, ctx->run.ssq_parts));
+    } else if (ds_layers) {
+        RUN(vcla_rmsnorm(w.x, D, ctx->norm_g, w.h, D, M, D, c.t_eps, dt, s));
+        RUN(gemm(ctx, s, w.h, D, ctx->lm_head, nullptr, nullptr, 0, lg, c.t_vocab, M, c.t_vocab, D, VCLA_EPI_NONE, 1, 0, 0, 0, nullptr, 0.f, &ctx->vlm));
+    } else if (gemv_norm(dt, M)) {
+        RUN(gemm(ctx, s, w.x, D, ctx->lm_head, nullptr, nullptr, 0, lg, c.t_vocab, M, c.t_vocab, D, VCLA_EPI_NONE, 1, 0, 0, 0, ctx->norm_g, c.t_eps, &ctx->vlm));
+    } else {
+        RUN(gemm(ctx, s, w.h, D, ctx->lm_head, nullptr, nullptr, 0, lg, c.t_vocab, M, c.t_vocab, D, VCLA_EPI_NONE, 1, 0, 0, 0, nullptr, 0.f, &ctx->vlm));
+    }
+    return VCLA_OK;
+}
+
 static int llama_prefill_impl(vcla_ctx* ctx, const void* inputs_embeds, int B, int T, int pos0, void* kv_cache, int ctx_max,
                               const int32_t* key_mask, float* logits, int all_logits, void* ws, void* layer_tap, hipStream_t s);
 
@@ -879,8 +958,10 @@ extern "C" int vcla_llama_prefill(vcla_ctx* ctx, const void* inputs_embeds, int 
                  "rows; the 1-byte cache serves single-token steps) -- nothing was written");
     hipStream_t s = (hipStream_t)stream;
     if (layer_tap) return llama_prefill_impl(ctx, inputs_embeds, B, T, pos0, kv_cache, ctx_max, key_mask, logits, all_logits, ws, layer_tap, s);
-    const void* const key[8] = {inputs_embeds, kv_cache, key_mask, logits, ws, (const void*)(((intptr_t)B << 32) | (uint32_t)T),
-                                (const void*)(((intptr_t)pos0 << 32) | (uint32_t)ctx_max), (const void*)(intptr_t)(all_logits + 2 * c.t_fp8_mfma)};
+    struct { const void *inputs_embeds, *kv_cache, *key_mask, *logits, *ws; int B, T, pos0, ctx_max, all_logits, t_fp8_mfma; } key;
+    memset(&key, 0, sizeof key);
+    key.inputs_embeds = inputs_embeds; key.kv_cache = kv_cache; key.key_mask = key_mask; key.logits = logits; key.ws = ws;
+    key.B = B; key.T = T; key.pos0 = pos0; key.ctx_max = ctx_max; key.all_logits = all_logits; key.t_fp8_mfma = c.t_fp8_mfma;
     return run_macro(ctx->prefill_graph, key, s, [&](hipStream_t st) {
         return llama_prefill_impl(ctx, inputs_embeds, B, T, pos0, kv_cache, ctx_max, key_mask, logits, all_logits, ws, nullptr, st);
     });
@@ -893,9 +974,10 @@ static int llama_prefill_impl(vcla_ctx* ctx, const void* inputs_embeds, int B, i
     const size_t e = esz(ctx);
     const int D = c.t_hidden, M = B * T;
     LlamaWs w;
-    carve_llama(ctx, B, T, (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255), &w);
+    carve_llama(ctx, B, T, align256(ws), &w);
     ctx->run.splitk_ws = w.splitk;
-    struct Q8Scope { vcla_ctx* c; Q8Scope(vcla_ctx* c_, void* q, float* s_) : c(c_) { c->run.q8_ws = q; c->run.q8s_ws = s_; } ~Q8Scope() { c->run.q8_ws = nullptr; c->run.q8s_ws = nullptr; } } q8_scope(ctx, w.q8, w.q8s);
+    const RunScope scope(ctx);
+    ctx->run.q8_ws = w.q8; ctx->run.q8s_ws = w.q8s;
     VCLA_CHECK_HIP(hipMemcpyAsync(w.x, inputs_embeds, (size_t)M * D * e, hipMemcpyDeviceToDevice, s));
     for (int l = 0; l < c.t_layers; ++l) {
         // every layer's down_proj also emits the next norm into w.h (the final norm only when all rows need it)
@@ -903,9 +985,8 @@ static int llama_prefill_impl(vcla_ctx* ctx, const void* inputs_embeds, int B, i
         RUN(llama_layer(ctx, s, ctx->llama[l], w, l, B, T, pos0, nullptr, kv_cache, ctx_max, key_mask, l > 0, next_gamma));
         RUN(tap_copy(layer_tap, l, w.x, (size_t)M * D * e, s));
     }
-    const bool norm_fused = (dt == VCLA_F32) ? (M <= 8) : (M == 1);   // llama_layer's GEMV mode ignores next_gamma
     if (all_logits) {
-        if (norm_fused) RUN(vcla_rmsnorm(w.x, D, ctx->norm_g, w.h, D, M, D, c.t_eps, dt, s));
+        if (gemv_norm(dt, M)) RUN(vcla_rmsnorm(w.x, D, ctx->norm_g, w.h, D, M, D, c.t_eps, dt, s));   // llama_layer's GEMV mode ignores next_gamma
         RUN(tap_copy(layer_tap, c.t_layers, w.h, (size_t)M * D * e, s));
         if (logits)
             RUN(gemm(ctx, s, w.h, D, ctx->lm_head, nullptr, nullptr, 0, logits, c.t_vocab, M, c.t_vocab, D, VCLA_EPI_NONE, 1));
@@ -931,7 +1012,8 @@ static int decode_step_impl(vcla_ctx* ctx, hipStream_t s, const int64_t* ids_in,
     const vcla_model_cfg& c = ctx->c;
     const int dt = c.act_dtype;
     const int D = c.t_hidden;
-    struct Scope { vcla_ctx* c; explicit Scope(vcla_ctx* c_) : c(c_) { c->run.decode_step = true; } ~Scope() { c->run.decode_step = false; } } decode_scope(ctx);
+    const RunScope scope(ctx);
+    ctx->run.decode_step = true;
     if (!skip_embed) RUN(vcla_embed_splice(ids_in, ctx->embed, nullptr, nullptr, w.x, B, 1, 0, D, c.t_vocab, dt, s));   // else: w.x was filled by post_select_kernel
     float* lg = logits ? logits : w.logits;
     if (engine_step_ok(ctx, B)) {
@@ -956,26 +1038,7 @@ static int decode_step_impl(vcla_ctx* ctx, hipStream_t s, const int64_t* ids_in,
         RUN(vcla_engine_launch(&ea, s));
         if (fold) return VCLA_OK;
     } else {
-    for (int l = 0; l < c.t_layers; ++l)   // batched mode: the norms ride on the producing GEMMs, the last one is the final norm
-        RUN(llama_layer(ctx, s, ctx->llama[l], w, l, B, 1, pos0, pos_dev, kv_cache, ctx_max, key_mask, l > 0,
-                        l + 1 < c.t_layers ? ctx->llama[l + 1].ln1g : ctx->norm_g));
-    const LlamaLayer& L0 = ctx->llama[0];
-    const bool ds_layers = vcla_knobs_get().dstream && dt == VCLA_BF16 && B >= 2 && B <= 64 && D % 32 == 0 && c.t_inter % 32 == 0 &&
-                           ((L0.vqkv.frag && L0.vo.frag && L0.vgu.frag && L0.vd.frag) || (L0.vqkv.q8f && L0.vo.q8f && L0.vgu.q8f && L0.vd.q8f));
-    if (ds_layers && (ctx->vlm.frag || ctx->vlm.q8f)) {
-        // streaming layers leave the residual stream in w.x: final norm -> fragment-major, lm_head streamed the same way
-        const bool defer = vcla_knobs_get().ds_defer != 0 && D % 16 == 0;     // the last down_proj left gamma_final * x and its row statistics in w.h / w.ssq
-        if (!defer) RUN(vcla_rmsnorm_pack(w.x, D, ctx->norm_g, w.h, B, D, c.t_eps, s));
-        RUN(gemm_ds(ctx, s, w.h, ctx->lm_head, ctx->vlm, nullptr, 0, lg, c.t_vocab, nullptr, B, c.t_vocab, D, VCLA_EPI_NONE, 1,
-                    defer ? w.ssq : nullptr, ctx->run.ssq_parts));
-    } else if (ds_layers) {
-        RUN(vcla_rmsnorm(w.x, D, ctx->norm_g, w.h, D, B, D, c.t_eps, dt, s));
-        RUN(gemm(ctx, s, w.h, D, ctx->lm_head, nullptr, nullptr, 0, lg, c.t_vocab, B, c.t_vocab, D, VCLA_EPI_NONE, 1, 0, 0, 0, nullptr, 0.f, &ctx->vlm));
-    } else if ((dt == VCLA_F32) ? (B <= 8) : (B == 1)) {
-        RUN(gemm(ctx, s, w.x, D, ctx->lm_head, nullptr, nullptr, 0, lg, c.t_vocab, B, c.t_vocab, D, VCLA_EPI_NONE, 1, 0, 0, 0, ctx->norm_g, c.t_eps, &ctx->vlm));
-    } else {
-        RUN(gemm(ctx, s, w.h, D, ctx->lm_head, nullptr, nullptr, 0, lg, c.t_vocab, B, c.t_vocab, D, VCLA_EPI_NONE, 1, 0, 0, 0, nullptr, 0.f, &ctx->vlm));
-    }
+        RUN(decoder_rows(ctx, s, w, B, 1, pos0, pos_dev, kv_cache, ctx_max, key_mask, lg));
     }
     if (ids_out && samp) RUN(vcla_sample_launch(lg, c.t_vocab, B, c.t_vocab, n_hist0, pos_dev, samp, ids_out, s));
     else if (ids_out) RUN(vcla_argmax(lg, c.t_vocab, ids_out, B, c.t_vocab, s));
@@ -1003,7 +1066,7 @@ extern "C" int vcla_llama_decode_step(vcla_ctx* ctx, const int64_t* ids_in, int 
     VCLA_KNOBS_SCOPE();
     RUN(check_decode_args(ctx, ids_in, B, pos0, pos_dev, kv_cache, ctx_max, ws, ws_bytes));
     LlamaWs w;
-    carve_llama(ctx, B, 1, (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255), &w);
+    carve_llama(ctx, B, 1, align256(ws), &w);
     ctx->run.splitk_ws = w.splitk;
     if (engine_step_ok(ctx, B)) VCLA_CHECK_HIP(hipMemsetAsync(w.eng, 0, EG_WS_BYTES, (hipStream_t)stream));
     return decode_step_impl(ctx, (hipStream_t)stream, ids_in, B, pos0, pos_dev, advance_pos, kv_cache, ctx_max, key_mask,
@@ -1028,7 +1091,7 @@ extern "C" int vcla_llama_decode_loop_sampled(vcla_ctx* ctx, const int64_t* ids_
     if (n_steps == 0) return VCLA_OK;
     hipStream_t s = (hipStream_t)stream;
     LlamaWs w;
-    carve_llama(ctx, B, 1, (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255), &w);
+    carve_llama(ctx, B, 1, align256(ws), &w);
     ctx->run.splitk_ws = w.splitk;
     // w.ids holds the current token of every sequence; each step consumes it and overwrites it with the argmax.
     VCLA_CHECK_HIP(hipMemcpyAsync(w.ids, ids_in, (size_t)B * 8, hipMemcpyDeviceToDevice, s));
@@ -1057,41 +1120,13 @@ extern "C" int vcla_llama_decode_loop_sampled(vcla_ctx* ctx, const int64_t* ids_
         VCLA_CHECK_LAUNCH("post_select_kernel");
         return VCLA_OK;
     };
-    hipStreamCaptureStatus outer = hipStreamCaptureStatusNone;   // the caller captures this stream itself: the steps belong in its graph
-    if (use_graph && s != nullptr && hipStreamIsCapturing(s, &outer) != hipSuccess) { (void)hipGetLastError(); outer = hipStreamCaptureStatusNone; }
-    if (!use_graph || s == nullptr || outer != hipStreamCaptureStatusNone) {  // stream capture is illegal on the legacy default stream
-        for (int i = 0; i < n_steps; ++i) RUN(one_step(s));
-        return VCLA_OK;
-    }
-    // hipGraph path: capture one step once per (buffers, shapes) key, replay n_steps times.
-    auto& k = ctx->graph_key;
-    const vcla_knobs& kn = vcla_knobs_get();
-    const bool same = ctx->graph_exec && k.ids == (const void*)w.ids && k.kv == kv_cache && k.mask == (const void*)key_mask &&
-                      k.ws == ws && k.out == (const void*)ids_out && k.B == B && k.pos0 == pos0 && k.ctx_max == ctx_max &&
-                      k.pos_dev == (const void*)pos_dev && k.step_base == step_base && k.has_samp == (sampling != nullptr) &&
-                      memcmp(&k.knobs, &kn, sizeof kn) == 0 &&
-                      (!sampling || (k.n_hist0 == n_hist0 && memcmp(&k.samp, sampling, sizeof(*sampling)) == 0));
-    if (!same) {
-        if (ctx->graph_exec) { (void)hipGraphExecDestroy(ctx->graph_exec); ctx->graph_exec = nullptr; }
-        hipGraph_t graph = nullptr;
-        VCLA_CHECK_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        const int rc = one_step(s);
-        hipError_t ce = hipStreamEndCapture(s, &graph);
-        if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-        if (ce != hipSuccess) return vcla_fail(VCLA_ERR_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(ce));
-        hipError_t ie = hipGraphInstantiate(&ctx->graph_exec, graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);
-        if (ie != hipSuccess) { ctx->graph_exec = nullptr; return vcla_fail(VCLA_ERR_HIP, "hipGraphInstantiate failed: %s", hipGetErrorString(ie)); }
-        k.ids = w.ids; k.kv = kv_cache; k.mask = key_mask; k.ws = ws; k.out = ids_out; k.B = B; k.pos0 = pos0;
-        k.ctx_max = ctx_max; k.pos_dev = pos_dev; k.step_base = step_base;
-        k.has_samp = sampling != nullptr; k.n_hist0 = n_hist0; k.knobs = kn;
-        if (sampling) memcpy(&k.samp, sampling, sizeof(*sampling));
-        if (kn.macro_graph_debug) fprintf(stderr, "[vcla] decode graph %p: capture\n", (void*)&ctx->graph_exec);
-    } else if (kn.macro_graph_debug) {
-        fprintf(stderr, "[vcla] decode graph %p: replay\n", (void*)&ctx->graph_exec);
-    }
-    for (int left = n_steps; left > 0; --left) VCLA_CHECK_HIP(hipGraphLaunch(ctx->graph_exec, s));
-    return VCLA_OK;
+    // w.ids, not ids_in: the eos path calls the loop once per chunk of tokens with the next ids_in and keeps replaying one graph
+    struct { const void *ids, *kv_cache, *key_mask, *ws, *ids_out, *pos_dev; int B, pos0, ctx_max, has_samp, n_hist0; vcla_sample_args samp; } key;
+    memset(&key, 0, sizeof key);
+    key.ids = w.ids; key.kv_cache = kv_cache; key.key_mask = key_mask; key.ws = ws; key.ids_out = ids_out; key.pos_dev = pos_dev;
+    key.B = B; key.pos0 = pos0; key.ctx_max = ctx_max; key.has_samp = sampling != nullptr;
+    if (sampling) { key.n_hist0 = n_hist0; memcpy(&key.samp, sampling, sizeof(*sampling)); }
+    return run_steps(ctx->decode_graph, "decode", key, use_graph, n_steps, s, one_step);
 }
 
 // The persistent decode step bounds every wait; a wait that ran out leaves (site code | CU << 16) in the workspace.  Synchronises the stream.
@@ -1102,7 +1137,7 @@ extern "C" int vcla_llama_decode_status(vcla_ctx* ctx, int B, const void* ws, si
     VCLA_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
     if (!engine_step_ok(ctx, B)) return VCLA_OK;
     LlamaWs w;
-    carve_llama(ctx, B, 1, (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255), &w);
+    carve_llama(ctx, B, 1, align256(ws), &w);
     unsigned st[2] = {0, 0};
     VCLA_CHECK_HIP(hipMemcpy(st, (const char*)w.eng + EG_WS_STATE_OFF, sizeof st, hipMemcpyDeviceToHost));
     if (st[1]) return vcla_fail(VCLA_ERR_HIP, "decode engine: a wait timed out (site 0x%x on CU %u after %u launches); its output is invalid.  The persistent launch needs all %d CUs to itself "
@@ -1130,33 +1165,11 @@ extern "C" size_t vcla_llama_verify_workspace_bytes(const vcla_ctx* ctx, int ctx
 static int verify_iter_impl(vcla_ctx* ctx, hipStream_t s, const vcla_lookup_args* a, int pos0, int32_t* pos_dev, void* kv_cache, int ctx_max,
                             const int32_t* key_mask, const LlamaWs& w) {
     const vcla_model_cfg& c = ctx->c;
-    const int dt = c.act_dtype, D = c.t_hidden, R = a->k + 1;
-    struct Scope {
-        vcla_ctx* c;
-        explicit Scope(vcla_ctx* c_) : c(c_) { c->run.decode_step = true; c->run.verify = true; }
-        ~Scope() { c->run.decode_step = false; c->run.verify = false; }
-    } scope(ctx);
-    RUN(vcla_embed_splice(a->row, ctx->embed, nullptr, nullptr, w.x, 1, R, 0, D, c.t_vocab, dt, s));
-    for (int l = 0; l < c.t_layers; ++l)
-        RUN(llama_layer(ctx, s, ctx->llama[l], w, l, 1, R, pos0, pos_dev, kv_cache, ctx_max, key_mask, l > 0,
-                        l + 1 < c.t_layers ? ctx->llama[l + 1].ln1g : ctx->norm_g));
-    // final norm + lm_head over the R rows: decode_step_impl's tail with B = R
-    const LlamaLayer& L0 = ctx->llama[0];
-    const bool ds_layers = vcla_knobs_get().dstream && dt == VCLA_BF16 && R >= 2 && D % 32 == 0 && c.t_inter % 32 == 0 &&
-                           ((L0.vqkv.frag && L0.vo.frag && L0.vgu.frag && L0.vd.frag) || (L0.vqkv.q8f && L0.vo.q8f && L0.vgu.q8f && L0.vd.q8f));
-    if (ds_layers && (ctx->vlm.frag || ctx->vlm.q8f)) {
-        const bool defer = vcla_knobs_get().ds_defer != 0 && D % 16 == 0;
-        if (!defer) RUN(vcla_rmsnorm_pack(w.x, D, ctx->norm_g, w.h, R, D, c.t_eps, s));
-        RUN(gemm_ds(ctx, s, w.h, ctx->lm_head, ctx->vlm, nullptr, 0, w.logits, c.t_vocab, nullptr, R, c.t_vocab, D, VCLA_EPI_NONE, 1,
-                    defer ? w.ssq : nullptr, ctx->run.ssq_parts));
-    } else if (ds_layers) {
-        RUN(vcla_rmsnorm(w.x, D, ctx->norm_g, w.h, D, R, D, c.t_eps, dt, s));
-        RUN(gemm(ctx, s, w.h, D, ctx->lm_head, nullptr, nullptr, 0, w.logits, c.t_vocab, R, c.t_vocab, D, VCLA_EPI_NONE, 1, 0, 0, 0, nullptr, 0.f, &ctx->vlm));
-    } else if ((dt == VCLA_F32) ? (R <= 8) : (R == 1)) {
-        RUN(gemm(ctx, s, w.x, D, ctx->lm_head, nullptr, nullptr, 0, w.logits, c.t_vocab, R, c.t_vocab, D, VCLA_EPI_NONE, 1, 0, 0, 0, ctx->norm_g, c.t_eps, &ctx->vlm));
-    } else {
-        RUN(gemm(ctx, s, w.h, D, ctx->lm_head, nullptr, nullptr, 0, w.logits, c.t_vocab, R, c.t_vocab, D, VCLA_EPI_NONE, 1, 0, 0, 0, nullptr, 0.f, &ctx->vlm));
-    }
+    const int R = a->k + 1;
+    const RunScope scope(ctx);
+    ctx->run.decode_step = ctx->run.verify = true;
+    RUN(vcla_embed_splice(a->row, ctx->embed, nullptr, nullptr, w.x, 1, R, 0, c.t_hidden, c.t_vocab, c.act_dtype, s));
+    RUN(decoder_rows(ctx, s, w, 1, R, pos0, pos_dev, kv_cache, ctx_max, key_mask, w.logits));
     RUN(vcla_argmax(w.logits, c.t_vocab, w.ids, R, c.t_vocab, s));
     return vcla_lookup_step(w.ids, a, pos_dev, s);
 }
@@ -1178,39 +1191,14 @@ extern "C" int vcla_llama_verify_loop(vcla_ctx* ctx, const vcla_lookup_args* arg
     LlamaWs w;
     void* scratch = nullptr;
     size_t scratch_bytes = 0;
-    carve_verify(ctx, ctx_max, (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255), &w, &scratch, &scratch_bytes);
+    carve_verify(ctx, ctx_max, align256(ws), &w, &scratch, &scratch_bytes);
     ctx->run.splitk_ws = w.splitk;
     ctx->run.verify_scratch = scratch;
     ctx->run.verify_scratch_bytes = scratch_bytes;
     auto one_iter = [&](hipStream_t st) { return verify_iter_impl(ctx, st, args, pos0, pos_dev, kv_cache, ctx_max, key_mask, w); };
-    hipStreamCaptureStatus outer = hipStreamCaptureStatusNone;   // the caller captures this stream itself: the iterations belong in its graph
-    if (use_graph && s != nullptr && hipStreamIsCapturing(s, &outer) != hipSuccess) { (void)hipGetLastError(); outer = hipStreamCaptureStatusNone; }
-    if (!use_graph || s == nullptr || outer != hipStreamCaptureStatusNone) {
-        for (int i = 0; i < n_iters; ++i) RUN(one_iter(s));
-        return VCLA_OK;
-    }
-    auto& k = ctx->lookup_key;
-    const vcla_knobs& kn = vcla_knobs_get();
-    const bool same = ctx->lookup_exec && k.kv == kv_cache && k.mask == (const void*)key_mask && k.ws == ws && k.pos_dev == (const void*)pos_dev &&
-                      k.pos0 == pos0 && k.ctx_max == ctx_max && memcmp(&k.args, args, sizeof(*args)) == 0 && memcmp(&k.knobs, &kn, sizeof kn) == 0;
-    if (!same) {
-        if (ctx->lookup_exec) { (void)hipGraphExecDestroy(ctx->lookup_exec); ctx->lookup_exec = nullptr; }
-        hipGraph_t graph = nullptr;
-        VCLA_CHECK_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        const int rc = one_iter(s);
-        hipError_t ce = hipStreamEndCapture(s, &graph);
-        if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-        if (ce != hipSuccess) return vcla_fail(VCLA_ERR_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(ce));
-        hipError_t ie = hipGraphInstantiate(&ctx->lookup_exec, graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);
-        if (ie != hipSuccess) { ctx->lookup_exec = nullptr; return vcla_fail(VCLA_ERR_HIP, "hipGraphInstantiate failed: %s", hipGetErrorString(ie)); }
-        memset(&k, 0, sizeof k);
-        k.kv = kv_cache; k.mask = key_mask; k.ws = ws; k.pos_dev = pos_dev; k.pos0 = pos0; k.ctx_max = ctx_max;
-        memcpy(&k.args, args, sizeof(*args)); k.knobs = kn;
-        if (kn.macro_graph_debug) fprintf(stderr, "[vcla] lookup graph %p: capture\n", (void*)&ctx->lookup_exec);
-    } else if (kn.macro_graph_debug) {
-        fprintf(stderr, "[vcla] lookup graph %p: replay\n", (void*)&ctx->lookup_exec);
-    }
-    for (int left = n_iters; left > 0; --left) VCLA_CHECK_HIP(hipGraphLaunch(ctx->lookup_exec, s));
-    return VCLA_OK;
+    struct { const void *kv_cache, *key_mask, *ws, *pos_dev; int pos0, ctx_max; vcla_lookup_args args; } key;
+    memset(&key, 0, sizeof key);
+    key.kv_cache = kv_cache; key.key_mask = key_mask; key.ws = ws; key.pos_dev = pos_dev; key.pos0 = pos0; key.ctx_max = ctx_max;
+    memcpy(&key.args, args, sizeof(*args));
+    return run_steps(ctx->verify_graph, "lookup", key, use_graph, n_iters, s, one_iter);
 }
