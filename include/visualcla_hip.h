@@ -492,6 +492,61 @@ size_t vcla_llama_verify_workspace_bytes(const vcla_ctx* ctx, int ctx_max);
 int vcla_llama_verify_loop(vcla_ctx* ctx, const vcla_lookup_args* args, int pos0, int32_t* pos_dev, int n_iters, void* kv_cache,
                            int ctx_max, const int32_t* key_mask, void* ws, size_t ws_bytes, int use_graph, void* stream);
 
+/* ---------------------------------------------------------------- in-flight batching (slots)
+   HF generate (hf generation/utils.py, the per-token loop reached from models/visualcla/modeling_visualcla.py:382-391) runs a batch in
+   lock-step: `unfinished_sequences` pads a finished row until the longest row of the batch is done, and nothing enters before the call
+   returns.  Here every batch row is a SLOT with a position of its own: a slot whose request ended goes inactive and the host refills it
+   with the next request of a queue between two chunks of steps.  Additive entries; the ABI version stays 5. */
+
+/* vcla_attn_decode_fused with one position per sequence: workgroup (h, b) works at pos = row_pos[b] (device int32 [B]) -- RoPE of q
+   and the new k at that position (LlamaAttention.forward hf:llama/modeling_llama.py:217-281 with per-row position_ids), append at that
+   position of sequence b's cache, softmax over keys [0, pos] minus the key_mask holes of row b.  row_pos[b] < 0 or >= ctx_max: the
+   sequence is INACTIVE -- nothing is written to its cache, its output row is zero.  Row b equals the uniform entry at pos = row_pos[b]
+   bit for bit.  fp32 / bf16, head dim 32 / 64 / 128, bf16 cache only (no VCLA_KV_FP8); key_mask_ld >= ctx_max. */
+int vcla_attn_decode_rows(const void* qkv, void* k_cache, void* v_cache, const float* cos_tab, const float* sin_tab, void* out, int B, int H,
+                          int d, int ctx_max, const int32_t* row_pos, const int32_t* key_mask, int64_t key_mask_ld, float scale, int dtype,
+                          int out_frag, void* stream);
+
+/* vcla_sample with one history length per sequence: row b applies its processors over history[0 .. n_hist_rows[b])[b] and draws at
+   uniforms[n_hist_rows[b]][b] (hf:generation/logits_process.py, as vcla_sample); rows with a negative length are skipped (ids_out[b]
+   is left alone). */
+int vcla_sample_rows(float* logits, int64_t ld, int B, int V, const int32_t* n_hist_rows, const vcla_sample_args* args, int64_t* ids_out,
+                     void* stream);
+
+#define VCLA_SLOT_MAX_EOS 8
+#define VCLA_SLOT_SUMMARY_WORDS 4
+/* the slot table, all device memory (one captured step is valid for a whole queue) */
+typedef struct vcla_slot_args {
+    int B;                      /* slots = batch rows                                                                        */
+    int hist_cap;               /* rows of history[]                                                                         */
+    int n_eos;
+    int eos_ids[VCLA_SLOT_MAX_EOS];
+    int32_t* row_pos;           /* [B] position of the slot's next input token; < 0: the slot is inactive                    */
+    int32_t* count;             /* [B] tokens generated for the slot's request so far                                        */
+    const int32_t* budget;      /* [B] the request's max_new_tokens                                                          */
+    int32_t* hist_len;          /* [B] count[b] while the slot is active, else -1: the n_hist_rows of vcla_sample_rows; may be NULL */
+    int64_t* history;           /* [hist_cap, B] step-major generated ids, the layout vcla_sample_args.history reads          */
+    int64_t* cur;               /* [B] the id each slot feeds to the next step                                               */
+    int32_t* summary;           /* [VCLA_SLOT_SUMMARY_WORDS] word 0: slots active after the last step; word 1: arrival counter
+                                   of the launch, zero before the first step (the launch re-arms it); the rest is reserved    */
+} vcla_slot_args;
+
+/* The token bookkeeping of one slots step, one launch (the per-row form of hf generation/utils.py `unfinished_sequences` /
+   EosTokenCriteria / MaxLengthCriteria at the end of a generation step): ids [B] = the ids selected this step.  Active slot b:
+   history[count[b]][b] = id, count[b] += 1, row_pos[b] += 1, cur[b] = id; an eos id or count[b] >= budget[b] finishes it
+   (row_pos[b] = -1).  The embedding of cur[b] (table bf16 [V, D]) becomes row b of x [B, D] (act dtype), the next step's decoder
+   input.  Inactive slots keep their state. */
+int vcla_slot_step(const int64_t* ids, const vcla_slot_args* args, const void* embed_table, void* x, int D, int V, int dtype, void* stream);
+
+/* n_steps slots steps enqueued on `stream`, each: the decoder over the B slot rows with per-row positions (vcla_attn_decode_rows) ->
+   final norm + lm_head -> argmax (sampling NULL) or vcla_sample_rows at slots->hist_len (sampling->history must be slots->history)
+   -> vcla_slot_step.  The first step's input rows are the embeddings of slots->cur.  The per-token loop body of hf
+   generation/utils.py reached from models/visualcla/modeling_visualcla.py:382-391, for rows at unrelated positions.  use_graph != 0
+   captures one step (a graph slot of its own: the cached decode and lookup graphs stay) and replays it.  Never the persistent B = 1
+   step; bf16 K / V cache only; key_mask optional [B, ctx_max]; workspace vcla_llama_workspace_bytes of (B, 1). */
+int vcla_llama_decode_slots(vcla_ctx* ctx, const vcla_slot_args* slots, int n_steps, void* kv_cache, int ctx_max, const int32_t* key_mask,
+                            void* ws, size_t ws_bytes, int use_graph, const vcla_sample_args* sampling, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

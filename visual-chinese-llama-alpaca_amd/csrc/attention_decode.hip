@@ -6,6 +6,9 @@
 // Workgroup = one (b, h), 256 threads.  Scores: one key per thread (B = 1) or D/8 lanes per key row (batch decode), 16-byte
 // row loads, probabilities in LDS; P V: D/8 adjacent lanes own one value row, partial outputs reduced by shuffles + LDS.
 // Position / context length come from device memory (pos0 + *pos_dev) so the launch is hipGraph-replayable.
+// ROWS (vcla_attn_decode_rows, in-flight batching): one position PER SEQUENCE instead -- `pos_dev` is then the vector row_pos[B] and
+// workgroup (h, b) works at row_pos[b]; a sequence whose position is outside [0, ctx_max) is inactive: nothing is appended, its output
+// row is zero.  Same code otherwise: row b equals, bit for bit, the uniform form at pos = row_pos[b].
 #include "vcla_common.h"
 #include <stdlib.h>
 
@@ -66,7 +69,7 @@ template <> struct Raw8<bf16_t> {
 // NW = waves per workgroup.  4 everywhere except the batch form at short contexts (NW = 2, see launch_decode): the batch launch
 // is bounded by the dependent chain of a workgroup times the number of ROUNDS of workgroups, not by bandwidth; 2-wave
 // workgroups fit 8 per CU, i.e. B * H = 2048 (b, h) pairs in ONE round instead of two.
-template <typename T, int D, bool COOP, int NW = 4>
+template <typename T, int D, bool COOP, int NW = 4, bool ROWS = false>
 __global__ __launch_bounds__(NW * 64) void attn_decode_kernel(const T* __restrict__ qkv, T* __restrict__ kc, T* __restrict__ vc,
                                                           const float* __restrict__ cos_tab, const float* __restrict__ sin_tab,
                                                           T* __restrict__ out, int H, int ctx_max, int pos0,
@@ -82,9 +85,24 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kernel(const T* __restric
     constexpr int NT = NW * 64;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int h = blockIdx.x, b = blockIdx.y;
-    const int pos = pos0 + (pos_dev ? *pos_dev : 0);   // position of the new token = number of cached keys
+    const int pos = ROWS ? pos_dev[b] : pos0 + (pos_dev ? *pos_dev : 0);   // position of the new token = number of cached keys
     constexpr int HALF = D / 2;
     const int HD = H * D;
+    if constexpr (ROWS) {
+        if (pos < 0 || pos >= ctx_max) {   // inactive sequence (workgroup-uniform): no append, a zero output row
+            if (out_frag_mt > 0) {
+                if (tid < D / 8) {
+                    const int k = h * D + tid * 8;
+                    T* dst = out + ((((int64_t)(k >> 5) * out_frag_mt + (b >> 4)) * 64 + ((k & 31) >> 3) * 16 + (b & 15)) << 3);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) Act<T>::st(dst + e, 0.f);
+                }
+            } else if (tid < D) {
+                Act<T>::st(out + (int64_t)b * HD + h * D + tid, 0.f);
+            }
+            return;
+        }
+    }
     const T* row = qkv + (int64_t)b * 3 * HD;
     T* kbase = kc + ((int64_t)b * H + h) * ctx_max * D;
     T* vbase = vc + ((int64_t)b * H + h) * ctx_max * D;
@@ -364,7 +382,7 @@ __device__ __forceinline__ float fp8_round(float x) {
 // that read q / k / v sum the slices, apply what the GEMM epilogue would have (the deferred-RMSNorm rstd of the row from its 16 partial
 // sums of squares, the fp8 weight scale of the column) and round to bf16: the values the reduce launch would have stored.
 struct QkvParts { int64_t slice; const float* ssq; const float* w_scale; float inv_hidden, eps; };
-template <int D, int NW, bool MASK, bool KV8 = false, bool QP = false>
+template <int D, int NW, bool MASK, bool KV8 = false, bool QP = false, bool ROWS = false>
 __global__ __launch_bounds__(NW * 64, NW == 2 ? 4 : 2) void attn_decode_flash_kernel(const void* __restrict__ qkv_, void* __restrict__ kc_, void* __restrict__ vc_,
                                                                 const float* __restrict__ cos_tab, const float* __restrict__ sin_tab,
                                                                 bf16_t* __restrict__ out, int H, int ctx_max, int pos0,
@@ -388,8 +406,19 @@ __global__ __launch_bounds__(NW * 64, NW == 2 ? 4 : 2) void attn_decode_flash_ke
     float* part = vnew + D;                                  // [NW][D + 2]: o[D], m, l
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int h = blockIdx.x, b = blockIdx.y;
-    const int pos = pos0 + (pos_dev ? *pos_dev : 0);         // position of the new token = number of cached keys
+    const int pos = ROWS ? pos_dev[b] : pos0 + (pos_dev ? *pos_dev : 0);   // position of the new token = number of cached keys
     const int HD = H * D;
+    if constexpr (ROWS) {
+        if (pos < 0 || pos >= ctx_max) {   // inactive sequence (workgroup-uniform): no append, a zero output row
+            if (tid < D / 8) {
+                const int k = h * D + tid * 8;
+                bf16_t* dst = out_frag_mt > 0 ? out + ((((int64_t)(k >> 5) * out_frag_mt + (b >> 4)) * 64 + ((k & 31) >> 3) * 16 + (b & 15)) << 3)
+                                              : out + (int64_t)b * HD + k;
+                *reinterpret_cast<uint4*>(dst) = make_uint4(0u, 0u, 0u, 0u);
+            }
+            return;
+        }
+    }
     const bf16_t* row = (const bf16_t*)qkv_ + (int64_t)b * 3 * HD;
     const float* prow = (const float*)qkv_ + (int64_t)b * 3 * HD;      // QP: slice 0 of this sequence's row
     unsigned char* kbase = (unsigned char*)kc_ + ((int64_t)b * H + h) * ctx_max * D * ESZ;
@@ -603,7 +632,7 @@ __global__ __launch_bounds__(NW * 64, NW == 2 ? 4 : 2) void attn_decode_flash_ke
 template <typename T, int D>
 static int launch_decode(const void* qkv, void* kc, void* vc, const float* cos_tab, const float* sin_tab, void* out, int B,
                          int H, int ctx_max, int pos0, const int32_t* pos_dev, const int32_t* key_mask, int64_t key_mask_ld,
-                         float scale, int out_frag, hipStream_t s, bool kv8 = false, const QkvParts* qp = nullptr) {
+                         float scale, int out_frag, hipStream_t s, bool kv8 = false, const QkvParts* qp = nullptr, bool rows = false) {
     const int sc_cap = (ctx_max + 63) & ~63;
     // batch form: 2-wave workgroups (8 per CU: one round for B * H <= 2048) while the context is short enough that the extra
     // passes over K and V (64 instead of 128 rows per pass) cost less than the second round of workgroups saves
@@ -618,8 +647,10 @@ static int launch_decode(const void* qkv, void* kc, void* vc, const float* cos_t
         // B * H fills the chip that way (16 per CU by waves), 4 waves otherwise; the row-major output needs 16-byte rows.
         const bool flash_ok = out_frag || (((int64_t)H * D) % 8 == 0 && vcla_aligned(out, 16));
         const bool small_wg = (int64_t)B * H >= 1024;
-#define FD_GO(NW_, MASK_, KV8_) attn_decode_flash_kernel<D, NW_, MASK_, KV8_><<<grid, NW_ * 64, 0, s>>>(qkv, kc, vc, cos_tab, sin_tab, \
+#define FD_GO(NW_, MASK_, KV8_) FD_GOR(NW_, MASK_, KV8_, false)
+#define FD_GOR(NW_, MASK_, KV8_, ROWS_) attn_decode_flash_kernel<D, NW_, MASK_, KV8_, false, ROWS_><<<grid, NW_ * 64, 0, s>>>(qkv, kc, vc, cos_tab, sin_tab, \
                                                     (bf16_t*)out, H, ctx_max, pos0, pos_dev, key_mask, key_mask_ld, scale, out_frag_mt)
+        VCLA_REQUIRE(!rows || (!qp && !kv8), VCLA_ERR_BAD_ARG, "attn_decode: per-row positions go with the bf16 cache and the plain qkv row");
         if (qp) {    // q / k / v arrive as two raw fp32 K slices of the qkv projection: 2-wave form only (batch decode, B * H >= 1024)
             if constexpr (D >= 64) {
                 VCLA_REQUIRE(flash_ok && small_wg, VCLA_ERR_BAD_ARG, "attn_decode: the split-qkv form needs B * H >= 1024 and a 16-byte aligned output");
@@ -645,6 +676,12 @@ static int launch_decode(const void* qkv, void* kc, void* vc, const float* cos_t
                 return vcla_fail(VCLA_ERR_BAD_SHAPE, "attn_decode: the fp8 cache needs head dim 64 or 128 (got %d)", D);
             }
         }
+        if (flash_ok && rows) {
+            if (small_wg) { if (key_mask) FD_GOR(2, true, false, true); else FD_GOR(2, false, false, true); }
+            else { if (key_mask) FD_GOR(4, true, false, true); else FD_GOR(4, false, false, true); }
+            VCLA_CHECK_LAUNCH("attn_decode_flash_kernel<rows>");
+            return VCLA_OK;
+        }
         if (flash_ok) {
             if (small_wg) { if (key_mask) FD_GO(2, true, false); else FD_GO(2, false, false); }
             else { if (key_mask) FD_GO(4, true, false); else FD_GO(4, false, false); }
@@ -652,8 +689,19 @@ static int launch_decode(const void* qkv, void* kc, void* vc, const float* cos_t
             return VCLA_OK;
         }
 #undef FD_GO
+#undef FD_GOR
     }
     const bool coop = (int64_t)B * H >= 512;
+    if (rows) {
+#define PD_GOR(COOP_, NW_) attn_decode_kernel<T, D, COOP_, NW_, true><<<grid, NW_ * 64, lds, s>>>((const T*)qkv, (T*)kc, (T*)vc, cos_tab, sin_tab, (T*)out, H, ctx_max, \
+                                                                                              pos0, pos_dev, key_mask, key_mask_ld, scale, sc_cap, out_frag_mt)
+        if (coop && NWs == 2) PD_GOR(true, 2);
+        else if (coop) PD_GOR(true, 4);
+        else PD_GOR(false, 4);
+#undef PD_GOR
+        VCLA_CHECK_LAUNCH("attn_decode_kernel<rows>");
+        return VCLA_OK;
+    }
     if (coop && NWs == 2)
         attn_decode_kernel<T, D, true, 2><<<grid, 128, lds, s>>>((const T*)qkv, (T*)kc, (T*)vc, cos_tab, sin_tab, (T*)out, H, ctx_max, pos0,
                                                                  pos_dev, key_mask, key_mask_ld, scale, sc_cap, out_frag_mt);
@@ -669,7 +717,7 @@ static int launch_decode(const void* qkv, void* kc, void* vc, const float* cos_t
 
 static int attn_decode_entry(const void* qkv, void* k_cache, void* v_cache, const float* cos_tab, const float* sin_tab, void* out, int B, int H, int d,
                              int ctx_max, int pos0, const int32_t* pos_dev, const int32_t* key_mask, int64_t key_mask_ld, float scale, int dtype, int out_frag,
-                             void* stream, const QkvParts* qp);
+                             void* stream, const QkvParts* qp, bool rows = false);
 
 extern "C" int vcla_attn_decode_fused_parts(const float* qkv_parts, int64_t slice_stride, const float* row_ssq, const float* w_scale, float norm_eps,
                                             void* k_cache, void* v_cache, const float* cos_tab, const float* sin_tab, void* out, int B, int H, int d,
@@ -693,10 +741,21 @@ extern "C" int vcla_attn_decode_fused(const void* qkv, void* k_cache, void* v_ca
                              nullptr);
 }
 
+extern "C" int vcla_attn_decode_rows(const void* qkv, void* k_cache, void* v_cache, const float* cos_tab, const float* sin_tab, void* out, int B, int H,
+                                     int d, int ctx_max, const int32_t* row_pos, const int32_t* key_mask, int64_t key_mask_ld, float scale, int dtype,
+                                     int out_frag, void* stream) {
+    VCLA_KNOBS_SCOPE();
+    VCLA_REQUIRE(row_pos, VCLA_ERR_BAD_ARG, "attn_decode_rows: row_pos is NULL");
+    VCLA_REQUIRE(!(dtype & VCLA_KV_FP8), VCLA_ERR_BAD_DTYPE, "attn_decode_rows: the e4m3 K/V cache is not supported");
+    VCLA_REQUIRE(!key_mask || key_mask_ld >= ctx_max, VCLA_ERR_BAD_ARG, "attn_decode_rows: key_mask_ld %lld < ctx_max %d", (long long)key_mask_ld, ctx_max);
+    return attn_decode_entry(qkv, k_cache, v_cache, cos_tab, sin_tab, out, B, H, d, ctx_max, 0, row_pos, key_mask, key_mask_ld, scale, dtype, out_frag, stream,
+                             nullptr, /*rows=*/true);
+}
+
 static int attn_decode_entry(const void* qkv, void* k_cache, void* v_cache, const float* cos_tab,
                              const float* sin_tab, void* out, int B, int H, int d, int ctx_max, int pos0,
                              const int32_t* pos_dev, const int32_t* key_mask, int64_t key_mask_ld, float scale,
-                             int dtype, int out_frag, void* stream, const QkvParts* qp) {
+                             int dtype, int out_frag, void* stream, const QkvParts* qp, bool rows) {
     const bool kv8 = (dtype & VCLA_KV_FP8) != 0;
     dtype &= ~VCLA_KV_FP8;
     VCLA_REQUIRE(dtype == VCLA_F32 || dtype == VCLA_BF16, VCLA_ERR_BAD_DTYPE, "attn_decode: bad dtype %d", dtype);
@@ -711,7 +770,7 @@ static int attn_decode_entry(const void* qkv, void* k_cache, void* v_cache, cons
                  "attn_decode: out_frag needs bf16, B <= 64 (got %d) and H*d %% 32 == 0", B);
     if (B == 0) return VCLA_OK;
     hipStream_t s = (hipStream_t)stream;
-#define DEC_CASE(TT, DD) return launch_decode<TT, DD>(qkv, k_cache, v_cache, cos_tab, sin_tab, out, B, H, ctx_max, pos0, pos_dev, key_mask, key_mask_ld, scale, out_frag, s, kv8, qp)
+#define DEC_CASE(TT, DD) return launch_decode<TT, DD>(qkv, k_cache, v_cache, cos_tab, sin_tab, out, B, H, ctx_max, pos0, pos_dev, key_mask, key_mask_ld, scale, out_frag, s, kv8, qp, rows)
     if (dtype == VCLA_F32) {
         if (d == 32) DEC_CASE(float, 32);
         if (d == 64) DEC_CASE(float, 64);

@@ -191,8 +191,9 @@ struct vcla_ctx {
     } run;
     // cached graphs of the vision stack and of the prefill (~250 / ~290 launches, host-bound at B = 1; run_macro), two shapes in rotation
     // each (e.g. forward(all_logits) and generate()'s prefill, or two batch sizes); of one decode step and of one verify iteration
-    // (run_steps), apart so that a plain generate() after a prompt-lookup one still replays its decode graph
-    GraphCache vision_graph{2}, prefill_graph{2}, decode_graph{1}, verify_graph{1};
+    // (run_steps), apart so that a plain generate() after a prompt-lookup one still replays its decode graph; of one slots step
+    // (vcla_llama_decode_slots), apart for the same reason
+    GraphCache vision_graph{2}, prefill_graph{2}, decode_graph{1}, verify_graph{1}, slots_graph{1};
 };
 
 // ctx->run as it was when the scope opened is restored when it closes
@@ -245,7 +246,7 @@ extern "C" int vcla_ctx_create(const vcla_model_cfg* cfg, vcla_ctx** out) {
 static void drop_graphs(vcla_ctx* ctx) {
     // An exec may still be executing (its last hipGraphLaunch is asynchronous) and HIP does not promise deferred destruction on every ROCm
     // version: drain the device first.  Only when there is something to destroy -- registering the tensors of a fresh context costs nothing.
-    GraphCache* const caches[] = {&ctx->vision_graph, &ctx->prefill_graph, &ctx->decode_graph, &ctx->verify_graph};
+    GraphCache* const caches[] = {&ctx->vision_graph, &ctx->prefill_graph, &ctx->decode_graph, &ctx->verify_graph, &ctx->slots_graph};
     bool any = false;
     for (const GraphCache* g : caches)
         for (const GraphCache::Slot& sl : g->slots) any = any || sl.exec;
@@ -791,7 +792,7 @@ static bool stream_layers(const vcla_ctx* ctx, int M, int T) {
 // One decoder layer over M = B*T rows held in ws.x (updated in place).
 static int llama_layer(vcla_ctx* ctx, hipStream_t s, const LlamaLayer& L, const LlamaWs& w, int l, int B, int T, int pos0,
                        const int32_t* pos_dev, void* kv_cache, int ctx_max, const int32_t* key_mask, bool h_ready = false,
-                       const float* next_gamma = nullptr) {
+                       const float* next_gamma = nullptr, const int32_t* row_pos = nullptr) {
     const vcla_model_cfg& c = ctx->c;
     const int dt = c.act_dtype;
     const size_t e = esz(ctx);
@@ -829,7 +830,13 @@ static int llama_layer(vcla_ctx* ctx, hipStream_t s, const LlamaLayer& L, const 
         const bool a_def = defer && h_ready;
         const bool qkv_split = kn.ds_qkv_split && M > 32 && (int64_t)B * H >= 1024 && d >= 64 && ctx->run.splitk_ws && (size_t)2 * M * 3 * D * 4 <= SPLITK_WS_BYTES &&
                                (!a_def || ctx->run.ssq_parts == 16);
-        if (verify) {
+        if (row_pos) {
+            // a slots step (vcla_llama_decode_slots): every row at its own position; the plain qkv projection (the split form has no per-row variant)
+            RUN(gemm_ds(ctx, s, w.h, L.wqkv, L.vqkv, nullptr, 0, w.qkv, 3 * D, nullptr, M, 3 * D, D, VCLA_EPI_NONE, 0,
+                        a_def ? w.ssq : nullptr, a_def ? ctx->run.ssq_parts : 0));
+            RUN(vcla_attn_decode_rows(w.qkv, kc, vc, ctx->rope_cos, ctx->rope_sin, w.ao, B, H, d, ctx_max, row_pos, key_mask, ctx_max, scale_, dt,
+                                      /*out_frag=*/1, s));
+        } else if (verify) {
             RUN(gemm_ds(ctx, s, w.h, L.wqkv, L.vqkv, nullptr, 0, w.qkv, 3 * D, nullptr, M, 3 * D, D, VCLA_EPI_NONE, 0,
                         a_def ? w.ssq : nullptr, a_def ? ctx->run.ssq_parts : 0));
             RUN(vcla_attn_verify(w.qkv, kc, vc, ctx->rope_cos, ctx->rope_sin, w.ao, T, H, d, ctx_max, pos0, pos_dev, key_mask, scale_, dkv,
@@ -876,6 +883,9 @@ static int llama_layer(vcla_ctx* ctx, hipStream_t s, const LlamaLayer& L, const 
         // verify rows: RoPE + KV append + causal attention over the cache, position from pos_dev
         RUN(vcla_attn_verify(w.qkv, kc, vc, ctx->rope_cos, ctx->rope_sin, w.ao, T, H, d, ctx_max, pos0, pos_dev, key_mask, scale, dkv, 0,
                              ctx->run.verify_scratch, ctx->run.verify_scratch_bytes, s));
+    } else if (T == 1 && row_pos) {
+        // a slots step: the same launch with one position per row
+        RUN(vcla_attn_decode_rows(w.qkv, kc, vc, ctx->rope_cos, ctx->rope_sin, w.ao, B, H, d, ctx_max, row_pos, key_mask, ctx_max, scale, dt, 0, s));
     } else if (T == 1) {
         // decode: RoPE + KV append + attention over the cache in one launch
         RUN(vcla_attn_decode_fused(w.qkv, kc, vc, ctx->rope_cos, ctx->rope_sin, w.ao, B, H, d, ctx_max, pos0, pos_dev, key_mask,
@@ -915,12 +925,12 @@ static int llama_layer(vcla_ctx* ctx, hipStream_t s, const LlamaLayer& L, const 
 // The decoder over the B x T rows in w.x of a decode step (T = 1) or a verify iteration (B = 1), then the final norm + lm_head into lg
 // [B * T, vocab].  The norms ride on the producing GEMMs; the last layer's emits the final norm.
 static int decoder_rows(vcla_ctx* ctx, hipStream_t s, const LlamaWs& w, int B, int T, int pos0, int32_t* pos_dev, void* kv_cache,
-                        int ctx_max, const int32_t* key_mask, float* lg) {
+                        int ctx_max, const int32_t* key_mask, float* lg, const int32_t* row_pos = nullptr) {
     const vcla_model_cfg& c = ctx->c;
     const int dt = c.act_dtype, D = c.t_hidden, M = B * T;
     for (int l = 0; l < c.t_layers; ++l)
         RUN(llama_layer(ctx, s, ctx->llama[l], w, l, B, T, pos0, pos_dev, kv_cache, ctx_max, key_mask, l > 0,
-                        l + 1 < c.t_layers ? ctx->llama[l + 1].ln1g : ctx->norm_g));
+                        l + 1 < c.t_layers ? ctx->llama[l + 1].ln1g : ctx->norm_g, row_pos));
     const bool ds_layers = stream_layers(ctx, M, T);
     if (ds_layers && (ctx->vlm.frag || ctx->vlm.q8f)) {
         // streaming layers leave the residual stream in w.x: final norm -> fragment-major, lm_head streamed the same way
@@ -1201,4 +1211,46 @@ extern "C" int vcla_llama_verify_loop(vcla_ctx* ctx, const vcla_lookup_args* arg
     key.kv_cache = kv_cache; key.key_mask = key_mask; key.ws = ws; key.pos_dev = pos_dev; key.pos0 = pos0; key.ctx_max = ctx_max;
     memcpy(&key.args, args, sizeof(*args));
     return run_steps(ctx->verify_graph, "lookup", key, use_graph, n_iters, s, one_iter);
+}
+
+// ------------------------------------------------------------------ in-flight batching: decode steps over slots at unrelated positions
+// One step: the decoder over the B slot rows with per-row positions, final norm + lm_head, argmax or the per-row sampler, the slot
+// bookkeeping (slots.hip).  Everything a step reads -- positions, counts, budgets, history, current ids -- lives in device memory, so one
+// captured step serves the whole queue whatever the host admits between two chunks.
+extern "C" int vcla_llama_decode_slots(vcla_ctx* ctx, const vcla_slot_args* slots, int n_steps, void* kv_cache, int ctx_max, const int32_t* key_mask,
+                                       void* ws, size_t ws_bytes, int use_graph, const vcla_sample_args* sampling, void* stream) {
+    VCLA_KNOBS_SCOPE();
+    VCLA_REQUIRE(ctx && ctx->finalized && ctx->c.t_layers > 0, VCLA_ERR_BAD_ARG, "llama_decode_slots: context not finalized, or vision-only");
+    RUN(slot_args_check(slots, "llama_decode_slots"));
+    const vcla_model_cfg& c = ctx->c;
+    const int B = slots->B;
+    VCLA_REQUIRE(kv_cache && ws && n_steps >= 0, VCLA_ERR_BAD_ARG, "llama_decode_slots: null pointer or n_steps < 0");
+    VCLA_REQUIRE(ctx_max > 0 && ctx_max <= c.t_max_pos, VCLA_ERR_BAD_SHAPE, "llama_decode_slots: ctx_max=%d (max_pos %d)", ctx_max, c.t_max_pos);
+    VCLA_REQUIRE(!c.t_kv_fp8, VCLA_ERR_BAD_ARG, "llama_decode_slots: the e4m3 K/V cache is not supported");
+    VCLA_REQUIRE(c.act_dtype != VCLA_BF16 || c.t_hidden % 8 == 0, VCLA_ERR_BAD_SHAPE, "llama_decode_slots: hidden size %d is not a multiple of 8", c.t_hidden);
+    VCLA_REQUIRE(!sampling || (slots->hist_len && sampling->history == slots->history), VCLA_ERR_BAD_ARG,
+                 "llama_decode_slots: sampling needs slots->hist_len and reads the slots' own history buffer");
+    VCLA_REQUIRE(ws_bytes >= vcla_llama_workspace_bytes(ctx, B, 1), VCLA_ERR_WORKSPACE, "llama_decode_slots: workspace %zu < %zu bytes", ws_bytes,
+                 vcla_llama_workspace_bytes(ctx, B, 1));
+    if (n_steps == 0) return VCLA_OK;
+    hipStream_t s = (hipStream_t)stream;
+    LlamaWs w;
+    carve_llama(ctx, B, 1, align256(ws), &w);
+    ctx->run.splitk_ws = w.splitk;
+    // the first step's decoder input; every later one comes from the slot bookkeeping launch that ends the step before it
+    RUN(vcla_embed_splice(slots->cur, ctx->embed, nullptr, nullptr, w.x, B, 1, 0, c.t_hidden, c.t_vocab, c.act_dtype, s));
+    auto one_step = [&](hipStream_t st) -> int {
+        const RunScope scope(ctx);
+        ctx->run.decode_step = true;
+        RUN(decoder_rows(ctx, st, w, B, 1, 0, nullptr, kv_cache, ctx_max, key_mask, w.logits, slots->row_pos));
+        if (sampling) RUN(vcla_sample_launch(w.logits, c.t_vocab, B, c.t_vocab, 0, nullptr, sampling, w.ids, st, slots->hist_len));
+        else RUN(vcla_argmax(w.logits, c.t_vocab, w.ids, B, c.t_vocab, st));
+        return vcla_slot_step(w.ids, slots, ctx->embed, w.x, c.t_hidden, c.t_vocab, c.act_dtype, st);
+    };
+    struct { const void *kv_cache, *key_mask, *ws; int ctx_max, has_samp; vcla_slot_args slots; vcla_sample_args samp; } key;
+    memset(&key, 0, sizeof key);
+    key.kv_cache = kv_cache; key.key_mask = key_mask; key.ws = ws; key.ctx_max = ctx_max; key.has_samp = sampling != nullptr;
+    memcpy(&key.slots, slots, sizeof(*slots));
+    if (sampling) memcpy(&key.samp, sampling, sizeof(*sampling));
+    return run_steps(ctx->slots_graph, "slots", key, use_graph, n_steps, s, one_step);
 }

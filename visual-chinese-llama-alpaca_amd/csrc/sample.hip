@@ -50,8 +50,8 @@ struct SampleParams {
 static_assert(SAMPLE_THREADS * SAMPLE_PER_THREAD == VCLA_SAMPLE_MAX_VOCAB, "register slice must cover the largest vocabulary");
 
 __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(float* __restrict__ logits, int64_t ld, int V, int B, int n_hist,
-                                                                const int32_t* __restrict__ n_hist_dev, SampleParams a,
-                                                                int64_t* __restrict__ out) {
+                                                                const int32_t* __restrict__ n_hist_dev, const int32_t* __restrict__ n_hist_rows,
+                                                                SampleParams a, int64_t* __restrict__ out) {
     __shared__ int s_hist[SAMPLE_MAX_HIST];
     __shared__ unsigned s_seen[VCLA_SAMPLE_MAX_VOCAB / 32];   // one bit per token id: "already penalised"
     __shared__ int s_cnt[3];
@@ -60,7 +60,9 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(float* __restric
     __shared__ int s_kk, s_ncand;
     const int tid = threadIdx.x, b = blockIdx.x, lane = tid & 63;
     float* x = logits + (int64_t)b * ld;
-    int h = n_hist + (n_hist_dev ? *n_hist_dev : 0);
+    // n_hist_rows (vcla_sample_rows, in-flight batching): every sequence has its own history length; a negative one skips the sequence
+    int h = n_hist_rows ? n_hist_rows[b] : n_hist + (n_hist_dev ? *n_hist_dev : 0);
+    if (n_hist_rows && h < 0) return;   // workgroup-uniform, ahead of every barrier
     h = h < 0 ? 0 : (h > SAMPLE_MAX_HIST ? SAMPLE_MAX_HIST : h);
     for (int i = tid; i < h; i += SAMPLE_THREADS) s_hist[i] = (int)a.history[(int64_t)i * B + b];
     const bool penalise = a.repetition_penalty != 1.f && h > 0;
@@ -295,7 +297,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(float* __restric
 }
 
 int vcla_sample_launch(float* logits, int64_t ld, int B, int V, int n_hist, const int32_t* n_hist_dev, const vcla_sample_args* a,
-                       int64_t* out, hipStream_t s) {
+                       int64_t* out, hipStream_t s, const int32_t* n_hist_rows) {
     VCLA_REQUIRE(logits && a && out, VCLA_ERR_BAD_ARG, "sample: null pointer");
     VCLA_REQUIRE(B >= 0 && V > 0 && V <= VCLA_SAMPLE_MAX_VOCAB && ld >= V && n_hist >= 0, VCLA_ERR_BAD_SHAPE,
                  "sample: B=%d V=%d (max %d) ld=%lld n_hist=%d", B, V, VCLA_SAMPLE_MAX_VOCAB, (long long)ld, n_hist);
@@ -304,7 +306,7 @@ int vcla_sample_launch(float* logits, int64_t ld, int B, int V, int n_hist, cons
                  a->min_tokens_to_keep >= 1 && a->n_eos >= 0 && a->n_eos <= VCLA_SAMPLE_MAX_EOS, VCLA_ERR_BAD_ARG,
                  "sample: temperature=%g repetition_penalty=%g top_p=%g no_repeat_ngram_size=%d min_tokens_to_keep=%d n_eos=%d", a->temperature,
                  a->repetition_penalty, a->top_p, a->no_repeat_ngram_size, a->min_tokens_to_keep, a->n_eos);
-    VCLA_REQUIRE(a->history || (n_hist == 0 && !n_hist_dev), VCLA_ERR_BAD_ARG, "sample: history is NULL but tokens were generated");
+    VCLA_REQUIRE(a->history || (n_hist == 0 && !n_hist_dev && !n_hist_rows), VCLA_ERR_BAD_ARG, "sample: history is NULL but tokens were generated");
     if (B == 0) return VCLA_OK;
     SampleParams p;
     p.repetition_penalty = a->repetition_penalty;
@@ -322,7 +324,7 @@ int vcla_sample_launch(float* logits, int64_t ld, int B, int V, int n_hist, cons
     p.kept_ids = a->kept_ids;
     p.kept_probs = a->kept_probs;
     p.n_kept = a->n_kept;
-    sample_kernel<<<B, SAMPLE_THREADS, 0, s>>>(logits, ld, V, B, n_hist, n_hist_dev, p, out);
+    sample_kernel<<<B, SAMPLE_THREADS, 0, s>>>(logits, ld, V, B, n_hist, n_hist_dev, n_hist_rows, p, out);
     VCLA_CHECK_LAUNCH("sample_kernel");
     return VCLA_OK;
 }
@@ -330,4 +332,10 @@ int vcla_sample_launch(float* logits, int64_t ld, int B, int V, int n_hist, cons
 extern "C" int vcla_sample(float* logits, int64_t ld, int B, int V, int n_hist, const int32_t* n_hist_dev, const vcla_sample_args* args,
                            int64_t* ids_out, void* stream) {
     return vcla_sample_launch(logits, ld, B, V, n_hist, n_hist_dev, args, ids_out, (hipStream_t)stream);
+}
+
+extern "C" int vcla_sample_rows(float* logits, int64_t ld, int B, int V, const int32_t* n_hist_rows, const vcla_sample_args* args, int64_t* ids_out,
+                                void* stream) {
+    VCLA_REQUIRE(n_hist_rows, VCLA_ERR_BAD_ARG, "sample_rows: n_hist_rows is NULL");
+    return vcla_sample_launch(logits, ld, B, V, 0, nullptr, args, ids_out, (hipStream_t)stream, n_hist_rows);
 }

@@ -40,9 +40,11 @@ int vcla_fail(int code, const char* fmt, ...);
         if (!(cond)) return vcla_fail(code, __VA_ARGS__);                                     \
     } while (0)
 
-// sample.hip: the launch behind vcla_sample, shared with the decode loop
+// sample.hip: the launch behind vcla_sample / vcla_sample_rows, shared with the decode loops (n_hist_rows: one history length per sequence)
 int vcla_sample_launch(float* logits, int64_t ld, int B, int V, int n_hist, const int32_t* n_hist_dev, const vcla_sample_args* a,
-                       int64_t* out, hipStream_t s);
+                       int64_t* out, hipStream_t s, const int32_t* n_hist_rows = nullptr);
+// slots.hip: validation of a slot table, shared with the slots loop
+int slot_args_check(const vcla_slot_args* a, const char* who);
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a property of (kernel, DEVICE): raise it once per device a kernel instantiation
 // is launched on (`done` = a static flag array of that instantiation), not once per process

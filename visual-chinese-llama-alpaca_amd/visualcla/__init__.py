@@ -7,6 +7,7 @@ from .modeling_utils import (
     DEFAULT_GENERATION_CONFIG,
     chat,
     chat_in_stream,
+    chat_many,
     get_model_and_processor,
     get_model_and_tokenizer_and_processor,
     hijack_samplers,
@@ -14,6 +15,6 @@ from .modeling_utils import (
 
 __all__ = [
     "VisualCLAModel", "VisualCLAConfig", "VisualCLAProcessor", "get_model_and_tokenizer_and_processor",
-    "get_model_and_processor", "chat", "chat_in_stream", "hijack_samplers", "DEFAULT_GENERATION_CONFIG",
+    "get_model_and_processor", "chat", "chat_many", "chat_in_stream", "hijack_samplers", "DEFAULT_GENERATION_CONFIG",
     "visualcla_7b_config",
 ]

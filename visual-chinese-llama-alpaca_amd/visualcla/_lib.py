@@ -135,6 +135,33 @@ def lookup_args(k, ngram_max, budget, eos_ids, row, history, out, state, filler=
     return a
 
 
+SLOT_MAX_EOS = 8            # VCLA_SLOT_MAX_EOS
+SLOT_SUMMARY_WORDS = 4      # VCLA_SLOT_SUMMARY_WORDS: slots still active, the launch's arrival counter, two reserved words
+
+
+class SlotArgs(C.Structure):
+    _fields_ = [
+        ("B", C.c_int), ("hist_cap", C.c_int), ("n_eos", C.c_int), ("eos_ids", C.c_int * SLOT_MAX_EOS),
+        ("row_pos", C.c_void_p), ("count", C.c_void_p), ("budget", C.c_void_p), ("hist_len", C.c_void_p),
+        ("history", C.c_void_p), ("cur", C.c_void_p), ("summary", C.c_void_p),
+    ]
+
+
+def slot_args(eos_ids, row_pos, count, budget, hist_len, history, cur, summary):
+    """vcla_slot_args over device tensors: row_pos / count / budget / hist_len int32 [B], history int64 [cap, B], cur int64 [B],
+    summary int32 [SLOT_SUMMARY_WORDS]"""
+    eos_ids = list(eos_ids)
+    if len(eos_ids) > SLOT_MAX_EOS:
+        raise ValueError(f"in-flight batching takes at most {SLOT_MAX_EOS} eos ids (got {len(eos_ids)})")
+    a = SlotArgs()
+    a.B, a.hist_cap, a.n_eos = int(row_pos.numel()), int(history.shape[0]), len(eos_ids)
+    for i, e in enumerate(eos_ids):
+        a.eos_ids[i] = int(e)
+    a.row_pos, a.count, a.budget, a.hist_len = ptr(row_pos), ptr(count), ptr(budget), ptr(hist_len)
+    a.history, a.cur, a.summary = ptr(history), ptr(cur), ptr(summary)
+    return a
+
+
 # every symbol include/visualcla_hip.h declares: name -> (restype, argtypes)
 _vp, _i, _i64, _f, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
 SYMBOLS = {
@@ -179,6 +206,10 @@ SYMBOLS = {
     "vcla_lookup_step": (_i, [_vp, C.POINTER(LookupArgs), _vp, _vp]),
     "vcla_llama_verify_workspace_bytes": (_sz, [_vp, _i]),
     "vcla_llama_verify_loop": (_i, [_vp, C.POINTER(LookupArgs), _i, _vp, _i, _vp, _i, _vp, _vp, _sz, _i, _vp]),
+    "vcla_attn_decode_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i64, _f, _i, _i, _vp]),
+    "vcla_sample_rows": (_i, [_vp, _i64, _i, _i, _vp, C.POINTER(SampleArgs), _vp, _vp]),
+    "vcla_slot_step": (_i, [_vp, C.POINTER(SlotArgs), _vp, _vp, _i, _i, _i, _vp]),
+    "vcla_llama_decode_slots": (_i, [_vp, C.POINTER(SlotArgs), _i, _vp, _i, _vp, _vp, _sz, _i, C.POINTER(SampleArgs), _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -1,0 +1,222 @@
+"""In-flight batching, host side: the request queue and the slot table behind `VisualCLAModel.generate_many`.
+
+A decode batch of B rows is B SLOTS.  Every slot holds one request at a position of its own; a slot whose request ended (eos, or its
+token budget) is refilled with the next request of the queue at the next boundary, `steps_per_sync` decode steps later.  This module
+owns the queue, the slot table and the rules by which the requests admitted at one boundary are prefilled together; it knows nothing of
+the device (the stepper is whoever calls `after_chunk` -- csrc/slots.hip through generate_many, or a fake one in the CPU tests).
+
+`slot_step_model` is the pure-Python statement of what the bookkeeping kernel `vcla_slot_step` does to the slot state; the GPU tests
+compare the kernel with it.
+"""
+from __future__ import annotations
+
+from collections import deque
+from dataclasses import dataclass, field
+from typing import Callable, Dict, List, Optional, Sequence
+
+
+def round_up(x: int, m: int) -> int:
+    return (int(x) + m - 1) // m * m
+
+
+def slot_step_model(ids: Sequence[int], row_pos: List[int], count: List[int], budget: Sequence[int], history: List[List[int]],
+                    cur: List[int], eos_ids: Sequence[int], hist_len: Optional[List[int]] = None) -> int:
+    """One step of the slot bookkeeping (csrc/slots.hip), in place: `ids[b]` is the id selected for slot b this step.  An active slot
+    (row_pos[b] >= 0) stores it at history[count[b]][b], advances count and position, and finishes (row_pos[b] = -1) on an eos id or
+    when count[b] reaches budget[b]; inactive slots are left alone.  Returns the number of slots still active."""
+    n_active = 0
+    for b in range(len(row_pos)):
+        if row_pos[b] < 0:
+            continue
+        t = int(ids[b])
+        c = count[b]
+        if c < len(history):
+            history[c][b] = t
+        fin = c + 1 >= budget[b] or t in eos_ids
+        count[b] = c + 1
+        row_pos[b] = -1 if fin else row_pos[b] + 1
+        if hist_len is not None:
+            hist_len[b] = -1 if fin else c + 1
+        cur[b] = t
+        n_active += not fin
+    return n_active
+
+
+@dataclass
+class Group:
+    """requests admitted at one boundary that are prefilled as ONE left-padded batch"""
+    requests: List[int] = field(default_factory=list)
+    slots: List[int] = field(default_factory=list)
+    T: int = 0                  # longest prompt of the group = the position its rows decode from
+    image: bool = False
+
+
+class InflightScheduler:
+    """The queue (arrival order) and the slot table of one generate_many call.
+
+    prompt_lens[i]: positions request i's prompt occupies in the decoder (image positions included); budgets[i]: its max_new_tokens;
+    has_image[i].  Budgets are clipped to max_position_embeddings - T as generate() clips; a prompt that leaves no room raises
+    ValueError naming the request.  ctx_max = min(max_position_embeddings, round_up_64(max T + max budget)), once for the queue."""
+
+    def __init__(self, prompt_lens: Sequence[int], budgets: Sequence[int], has_image: Sequence[bool], max_batch: int,
+                 max_position_embeddings: int, image_at_head: bool = False, steps_per_sync: int = 8):
+        if max_batch < 1:
+            raise ValueError(f"max_batch must be at least 1 (got {max_batch})")
+        if steps_per_sync < 1:
+            raise ValueError(f"steps_per_sync must be at least 1 (got {steps_per_sync})")
+        self.n = len(prompt_lens)
+        self.T = [int(t) for t in prompt_lens]
+        self.has_image = [bool(x) for x in has_image]
+        self.max_pos = int(max_position_embeddings)
+        self.budget: List[int] = []
+        for i, (t, b) in enumerate(zip(self.T, budgets)):
+            if self.max_pos - t <= 0:
+                raise ValueError(f"request {i}: prompt of {t} tokens leaves no room under max_position_embeddings={self.max_pos}")
+            if int(b) < 1:
+                raise ValueError(f"request {i}: max_new_tokens must be at least 1 (got {b})")
+            self.budget.append(min(int(b), self.max_pos - t))
+        self.slots = min(int(max_batch), max(self.n, 1))
+        self.steps_per_sync = int(steps_per_sync)
+        self.image_at_head = bool(image_at_head)
+        self.cap = max(self.budget, default=1)                   # rows of the history / uniforms buffers
+        self.ctx_max = min(self.max_pos, round_up(max(self.T, default=0) + self.cap, 64))
+        self.queue = deque(range(self.n))
+        self.slot_req: List[Optional[int]] = [None] * self.slots
+        self.results: Dict[int, List[int]] = {}
+        self.decode_from: Dict[int, int] = {}                    # request -> T of its admission group = the position its slot decoded from
+        self.stats = {"requests": self.n, "slots": self.slots, "steps": 0, "tokens": 0, "admission_groups": 0, "slot_steps_active": 0,
+                      "slot_steps_total": 0}
+
+    # ------------------------------------------------------------------ admission
+    def free_slots(self) -> List[int]:
+        return [b for b, r in enumerate(self.slot_req) if r is None]
+
+    def _fits(self, g: Group, i: int) -> bool:
+        if g.image != self.has_image[i]:
+            return False                                         # generate() takes pixel_values for every row of a batch or for none
+        if self.image_at_head and g.image and self.T[i] != g.T:
+            return False                                         # a left-padded text mask behind the image columns: the mask _check_request refuses
+        t = max(g.T, self.T[i])                                  # a row decodes from the group's longest prompt
+        return all(t + self.budget[j] <= self.ctx_max for j in g.requests + [i])
+
+    def admit(self, free_slots: Sequence[int]) -> List[Group]:
+        """The next requests in arrival order, one per free slot, as the groups that are prefilled together."""
+        groups: List[Group] = []
+        for b in sorted(free_slots):
+            if not self.queue:
+                break
+            if self.slot_req[b] is not None:
+                raise ValueError(f"slot {b} still holds request {self.slot_req[b]}")
+            i = self.queue.popleft()
+            g = next((g for g in groups if self._fits(g, i)), None)
+            if g is None:
+                g = Group(image=self.has_image[i])
+                groups.append(g)
+            g.requests.append(i)
+            g.slots.append(b)
+            g.T = max(g.T, self.T[i])
+            self.slot_req[b] = i
+        for g in groups:
+            for i in g.requests:
+                self.decode_from[i] = g.T
+        self.stats["admission_groups"] += len(groups)
+        return groups
+
+    def _finish(self, b: int, tokens: Sequence[int]) -> None:
+        i = self.slot_req[b]
+        if i is None or i in self.results:
+            raise ValueError(f"slot {b}: no running request to finish")
+        self.results[i] = [int(t) for t in tokens]
+        self.stats["tokens"] += len(tokens)
+        self.slot_req[b] = None
+
+    def started(self, b: int, first_token: int, ended: bool) -> None:
+        """The first token of slot b's request came out of its prefill.  ended (an eos, or a budget of 1): the request is complete and
+        never occupies the slot past this boundary."""
+        if ended:
+            self._finish(b, [first_token])
+
+    # ------------------------------------------------------------------ after a chunk of steps
+    def after_chunk(self, n_steps: int, row_pos: Sequence[int], count: Sequence[int], tokens_of: Callable[[int, int], Sequence[int]],
+                    count_before: Optional[Sequence[int]] = None) -> List[int]:
+        """n_steps steps ran.  Slots whose request finished (row_pos < 0) are harvested -- tokens_of(slot, n) returns the slot's n tokens
+        -- and freed.  Returns them."""
+        self.stats["steps"] += n_steps
+        self.stats["slot_steps_total"] += n_steps * self.slots
+        done = []
+        for b, i in enumerate(self.slot_req):
+            if i is None:
+                continue
+            if count_before is not None:
+                self.stats["slot_steps_active"] += int(count[b]) - int(count_before[b])
+            if row_pos[b] < 0:
+                self._finish(b, tokens_of(b, int(count[b])))
+                done.append(b)
+        return done
+
+    @property
+    def running(self) -> int:
+        return sum(r is not None for r in self.slot_req)
+
+    @property
+    def finished(self) -> bool:
+        return not self.queue and self.running == 0
+
+    def ordered_results(self) -> List[List[int]]:
+        if len(self.results) != self.n:
+            raise ValueError(f"{self.n - len(self.results)} requests have not finished")
+        return [self.results[i] for i in range(self.n)]
+
+
+def step_bound(budgets: Sequence[int], slots: int, steps_per_sync: int) -> float:
+    """Upper bound on the decode steps of a queue: (sum(n_i) + N (c - 1)) / B + max(n_i) + c.  Until the queue empties every slot is
+    busy or inside a gap of at most c - 1 steps behind a finish; afterwards at most the longest request plus one chunk remains."""
+    if not len(budgets):
+        return 0.0
+    c = steps_per_sync
+    return (sum(budgets) + len(budgets) * (c - 1)) / slots + max(budgets) + c
+
+
+def static_batch_steps(budgets: Sequence[int], slots: int) -> int:
+    """decode steps of lock-step batches of `slots` requests in arrival order, each run to its longest budget"""
+    return sum(max(budgets[i:i + slots]) - 1 for i in range(0, len(budgets), slots))
+
+
+def simulate(budgets: Sequence[int], slots: int, steps_per_sync: int, eos_at: Optional[Dict[int, int]] = None, prompt_lens=None, has_image=None,
+             max_position_embeddings: int = 1 << 20, image_at_head: bool = False):
+    """Drives a scheduler with the host model of the slot step and a stepper that emits token (request, k) = 1000 * request + k, or the
+    eos id 0 as request i's eos_at[i]-th token.  Returns (scheduler, log of (boundary, slot, request) admissions)."""
+    n = len(budgets)
+    eos_at = eos_at or {}
+    sch = InflightScheduler(prompt_lens or [4] * n, budgets, has_image or [False] * n, slots, max_position_embeddings, image_at_head, steps_per_sync)
+    B = sch.slots
+    row_pos, count, bud, cur = [-1] * B, [0] * B, [0] * B, [0] * B
+    history = [[0] * B for _ in range(sch.cap)]
+    log = []
+
+    def tok(i, k):
+        return 0 if eos_at.get(i) == k else 1000 * (i + 1) + k
+    boundary = 0
+    while not sch.finished:
+        while True:                                              # a request that ends at its first token frees its slot at once
+            groups = sch.admit(sch.free_slots())
+            if not groups:
+                break
+            for g in groups:
+                for i, b in zip(g.requests, g.slots):
+                    log.append((boundary, b, i))
+                    first = tok(i, 1)
+                    ended = first == 0 or sch.budget[i] == 1
+                    sch.started(b, first, ended)
+                    if not ended:
+                        row_pos[b], count[b], bud[b], cur[b] = g.T, 1, sch.budget[i], first
+                        history[0][b] = first
+        if sch.finished:
+            break
+        before = list(count)
+        for _ in range(steps_per_sync):
+            ids = [tok(sch.slot_req[b], count[b] + 1) if sch.slot_req[b] is not None and row_pos[b] >= 0 else -7 for b in range(B)]
+            slot_step_model(ids, row_pos, count, bud, history, cur, [0])
+        sch.after_chunk(steps_per_sync, row_pos, count, lambda b, m: [history[k][b] for k in range(m)], before)
+        boundary += 1
+    return sch, log

@@ -164,6 +164,31 @@ def chat(model, image: Union[str, "Image.Image", torch.Tensor], text: str, histo
 
 
 @torch.inference_mode()
+def chat_many(model, items, generation_config=None, max_batch=64):
+    """The bulk form of chat(): items = [(image, text) or (image, text, history), ...] -> [(response, history), ...].  Every prompt is built as
+    chat() builds it, the queue is answered by model.generate_many (in-flight batching over max_batch slots) and every response is appended
+    to its item's history exactly as chat() appends it."""
+    encs, histories = [], []
+    for item in items:
+        if len(item) not in (2, 3):
+            raise ValueError("chat_many: every item is (image, text) or (image, text, history)")
+        history = item[2] if len(item) == 3 else []
+        gc, enc = _prepare(model, item[0], item[1], history, generation_config)
+        encs.append(enc)
+        histories.append(history)
+    if not encs:
+        return []
+    outs = model.generate_many([dict(input_ids=e.input_ids[0], attention_mask=e.attention_mask[0], pixel_values=e.pixel_values) for e in encs],
+                               max_batch=max_batch, generation_config=gc)
+    results = []
+    for toks, history in zip(outs, histories):
+        response = model.tokenizer.decode(toks, skip_special_tokens=True)
+        history.append({"type": "response", "value": response})
+        results.append((response, history))
+    return results
+
+
+@torch.inference_mode()
 def chat_in_stream(model, image: Union[str, "Image.Image", torch.Tensor], text: str, history=[], generation_config=None):
     """Generator of (response_so_far, history).  generate() runs in a worker thread and hands the growing id
     sequence over a queue from a per-token stopping-criteria callback (reference :215-225, :404-472)."""

@@ -1059,3 +1059,239 @@ class VisualCLAModel:
             logits = step_logits
         self._check_decode_status(B, ws)
         return generated.contiguous()
+
+    # ------------------------------------------------------------------ in-flight batching
+    @staticmethod
+    def _refuse_inflight_conflicts(gc, vocab_size: int = 0, kv_fp8: bool = False, max_budget: int = 0, leftover_kwargs: Optional[dict] = None) -> None:
+        """generate_many decodes on the device-resident slots loop (argmax or the device sampler, one floor for the whole queue): every setting
+        that needs more is refused by name, all of them in one message.  Needs no device."""
+        from types import SimpleNamespace
+        from .logits_processors import _HOST_ONLY_FIELDS, min_token_floor, needs_host_processors, refuse_unsupported
+        refuse_unsupported(gc, leftover_kwargs)
+        eos = VisualCLAModel._eos_list(gc)
+        bad = []
+        if int(gc.num_beams or 1) > 1:
+            bad.append(f"num_beams={gc.num_beams}")
+        if int(gc.num_return_sequences or 1) != 1:
+            bad.append(f"num_return_sequences={gc.num_return_sequences}")
+        if getattr(gc, "prompt_lookup_num_tokens", None) is not None:
+            bad.append(f"prompt_lookup_num_tokens={gc.prompt_lookup_num_tokens}")
+        if getattr(gc, "max_time", None) is not None:
+            bad.append("max_time")
+        floor = min_token_floor(gc, 0) if eos else 0
+        if eos and getattr(gc, "min_new_tokens", None) is None and floor > 0:
+            bad.append(f"min_length={gc.min_length} (its floor depends on each prompt's length; use min_new_tokens)")
+        for f in _HOST_ONLY_FIELDS:
+            if needs_host_processors(SimpleNamespace(do_sample=getattr(gc, "do_sample", None), **{f: getattr(gc, f, None)})):
+                bad.append(f"{f}={getattr(gc, f)!r}")
+        rp = gc.repetition_penalty if gc.repetition_penalty is not None else 1.0
+        sampler = bool(gc.do_sample) or rp != 1.0 or bool(gc.no_repeat_ngram_size) or floor > 0
+        if gc.do_sample and not 1 <= (gc.top_k if gc.top_k is not None else 0) <= _lib.SAMPLE_MAX_TOP_K:
+            bad.append(f"top_k={gc.top_k} while sampling (the device sampler takes 1..{_lib.SAMPLE_MAX_TOP_K})")
+        if len(eos) > _lib.SLOT_MAX_EOS or (floor > 0 and len(eos) > _lib.SAMPLE_MAX_EOS):
+            bad.append(f"eos_token_id with {len(eos)} ids (at most {_lib.SLOT_MAX_EOS}; {_lib.SAMPLE_MAX_EOS} with min_new_tokens)")
+        if sampler and vocab_size > _lib.SAMPLE_MAX_VOCAB:
+            bad.append(f"vocab_size={vocab_size} with logits processors or sampling (the device sampler takes {_lib.SAMPLE_MAX_VOCAB})")
+        if sampler and max_budget > _lib.SAMPLE_MAX_HIST:
+            bad.append(f"max_new_tokens={max_budget} with logits processors or sampling (the device sampler sees {_lib.SAMPLE_MAX_HIST} tokens)")
+        if kv_fp8:
+            bad.append("the e4m3 K/V cache (enable_fp8_decode(kv_cache=True))")
+        if bad:
+            raise ValueError("generate_many (in-flight batching) cannot be combined with " + ", ".join(bad))
+
+    def _inflight_request(self, i: int, r) -> dict:
+        """one entry of generate_many's `requests` -> ids [T] int64, pixel_values [C, H, W] or None, attention_mask [T] or None (on the device)"""
+        if not isinstance(r, dict) or r.get("input_ids") is None:
+            raise ValueError(f"request {i}: a dict with `input_ids` is required")
+        unknown = set(r) - {"input_ids", "pixel_values", "attention_mask", "max_new_tokens"}
+        if unknown:
+            raise ValueError(f"request {i}: unknown keys {sorted(unknown)}")
+
+        def row(x, dims, what):
+            if x is None:
+                return None
+            x = torch.as_tensor(x)
+            if x.dim() == dims + 1 and x.shape[0] == 1:
+                x = x[0]
+            if x.dim() != dims:
+                raise ValueError(f"request {i}: {what} must hold one prompt, got shape {tuple(x.shape)}")
+            return x.to(self._device)
+        ids = row(r["input_ids"], 1, "input_ids").long()
+        am = row(r.get("attention_mask"), 1, "attention_mask")
+        if am is not None and am.shape != ids.shape:
+            raise ValueError(f"request {i}: attention_mask length {am.shape[0]} does not match input_ids length {ids.shape[0]}")
+        mnt = r.get("max_new_tokens")
+        if mnt is not None and (isinstance(mnt, bool) or int(mnt) < 1):
+            raise ValueError(f"request {i}: max_new_tokens must be a positive integer (got {mnt!r})")
+        return dict(ids=ids, px=row(r.get("pixel_values"), 3, "pixel_values"), am=am, max_new_tokens=mnt)
+
+    @torch.no_grad()
+    def generate_many(self, requests, max_batch: int = 64, generation_config=None, steps_per_sync: int = 8, use_graph: Optional[bool] = None, **kwargs):
+        """In-flight batching over a queue: -> List[LongTensor [n_i]] in request order, the NEW tokens of every request, its eos included
+        and nothing behind it.  requests: dicts with `input_ids` ([T] or [1, T]), optional `pixel_values`, `attention_mask`, `max_new_tokens`
+        (default: the config's budget by generate()'s rules for that prompt).  One generation config for the whole queue.
+
+        The decode batch is `max_batch` slots; a slot whose request ended is refilled with the next request every `steps_per_sync` steps
+        (visualcla/inflight.py, csrc/slots.hip).  result[i] is what generate() returns for request i alone at batch
+        size 1.  With do_sample=True that holds for the function, not for the random stream: request i draws with its own uniforms,
+        torch.rand(budget_i) taken from the device generator in request order when the request is admitted.
+
+        Greedy, and every config the device sampler covers (repetition penalty, no-repeat-ngram, min_new_tokens, temperature, top-k <= 256,
+        top-p); everything else is refused by name.  model.last_inflight_stats describes the call."""
+        from .inflight import InflightScheduler
+        from .logits_processors import new_token_budget
+        gc = self._resolve_generation_config(generation_config, kwargs)
+        t = self.config.text_config
+        reqs = [self._inflight_request(i, r) for i, r in enumerate(requests)]
+        Q = self.config.visual_resampler_config["num_query_tokens"]
+        lens = [int(r["ids"].numel()) + (Q if (self.image_at_head and r["px"] is not None) else 0) for r in reqs]
+        budgets = [int(r["max_new_tokens"]) if r["max_new_tokens"] is not None else new_token_budget(gc, T) for r, T in zip(reqs, lens)]
+        self._refuse_inflight_conflicts(gc, t["vocab_size"], bool(getattr(self, "_kv_fp8", False)),
+                                        max((min(b, t["max_position_embeddings"]) for b in budgets), default=0), kwargs)
+        # raises for a prompt that leaves no room, by index, before any kernel runs
+        sched = InflightScheduler(lens, budgets, [r["px"] is not None for r in reqs], max_batch, t["max_position_embeddings"], self.image_at_head,
+                                  steps_per_sync)
+        if use_graph is None:
+            use_graph = os.environ.get("VCLA_DECODE_GRAPH", "1") != "0"
+        if sched.slots == 1:
+            # max_batch = 1 or a single request: generate() per request (the persistent B = 1 step is the fast path there)
+            out = []
+            for i, r in enumerate(reqs):
+                toks = self.generate(input_ids=r["ids"][None], pixel_values=None if r["px"] is None else r["px"][None],
+                                     attention_mask=None if r["am"] is None else r["am"][None], generation_config=gc,
+                                     max_new_tokens=sched.budget[i], eos_token_id=gc.eos_token_id, use_graph=use_graph)[0].clone()   # (generate() may hand out its own buffer)
+                out.append(toks)
+                sched.stats["tokens"] += int(toks.numel())
+                sched.stats["steps"] += int(toks.numel()) - 1
+            sched.stats["slot_steps_active"] = sched.stats["slot_steps_total"] = sched.stats["steps"]
+            sched.stats["admission_groups"] = len(reqs)
+            self.last_inflight_stats = dict(sched.stats)
+            return out
+        cur_stream = torch.cuda.current_stream(self._device)
+        side = None
+        if use_graph and cur_stream.cuda_stream == 0:          # graph capture is illegal on the legacy default stream (as generate())
+            if getattr(self, "_side_stream", None) is None:
+                self._side_stream = torch.cuda.Stream(device=self._device)
+            side = self._side_stream
+            side.wait_stream(cur_stream)
+        with torch.cuda.device(self._device), torch.cuda.stream(side if side is not None else cur_stream):
+            out = self._inflight_on_stream(gc, reqs, sched, bool(use_graph))
+        if side is not None:
+            cur_stream.wait_stream(side)
+        return out
+
+    def _inflight_on_stream(self, gc, reqs, sched, use_graph: bool):
+        import time
+        from .logits_processors import min_token_floor
+        lib = _lib.load()
+        dev = self._device
+        t = self.config.text_config
+        B, ctx_max, cap = sched.slots, sched.ctx_max, sched.cap
+        eos = self._eos_list(gc)
+        rp = gc.repetition_penalty if gc.repetition_penalty is not None else 1.0
+        samp_kw = None
+        if gc.do_sample or rp != 1.0 or gc.no_repeat_ngram_size or (eos and min_token_floor(gc, 0) > 0):
+            samp_kw = self._device_sampling(gc, cap, 0)
+            if samp_kw is None:
+                raise ValueError("generate_many: the generation config does not map onto the device sampler")
+        # ---- the slot table: one int32 vector (row_pos | count | hist_len | budget | summary) so that a boundary is ONE copy to the host
+        W = _lib.SLOT_SUMMARY_WORDS
+        st = self._typed_buf("if_state", (4 * B + W,), torch.int32)
+        st.copy_(torch.tensor([-1] * B + [0] * B + [-1] * B + [0] * B + [0] * W, dtype=torch.int32))
+        row_pos, count, hist_len, budget, summary = st[:B], st[B:2 * B], st[2 * B:3 * B], st[3 * B:4 * B], st[4 * B:]
+        hist = self._typed_buf("if_hist", (cap, B), torch.int64)
+        cur = self._typed_buf("if_cur", (B,), torch.int64)
+        cur.zero_()
+        uni = self._typed_buf("if_uni", (cap, B), torch.float32) if gc.do_sample else None
+        H, d = t["num_attention_heads"], t["hidden_size"] // t["num_attention_heads"]
+        kv = self._typed_buf("if_kv", (t["num_hidden_layers"], 2, B, H, ctx_max, d), self._dtype)
+        km = self._typed_buf("if_km", (B, ctx_max), torch.int32)
+        km.fill_(1)
+        ws = self._buf("slots", lib.vcla_llama_workspace_bytes(self._ctx, B, 1))
+        slots = _lib.slot_args(eos, row_pos, count, budget, hist_len, hist, cur, summary)
+        samp = _lib.sample_args(uniforms=uni, history=hist, **samp_kw) if samp_kw is not None else None
+        count_h = [0] * B
+        t_adm = t_steps = 0.0
+        while not sched.finished:
+            t0 = time.perf_counter()
+            while True:                                         # a request whose first token ends it frees its slot within the boundary
+                groups = sched.admit(sched.free_slots())
+                if not groups:
+                    break
+                if uni is not None:                             # request i's own column of uniforms, drawn in request order
+                    for i, b in sorted((i, b) for g in groups for i, b in zip(g.requests, g.slots)):
+                        uni[:sched.budget[i], b] = torch.rand(sched.budget[i], device=dev)
+                for g in groups:
+                    self._inflight_admit(g, reqs, sched, eos, samp_kw, uni, kv, km, st, hist, cur, count_h)
+            t1 = time.perf_counter()
+            t_adm += t1 - t0
+            if sched.finished:
+                break
+            n = sched.steps_per_sync
+            _lib.check(lib.vcla_llama_decode_slots(self._ctx, C.byref(slots), n, kv.data_ptr(), ctx_max, km.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                   int(use_graph), C.byref(samp) if samp is not None else None, _lib.stream_ptr()))
+            host = st.tolist()                                  # the one synchronisation of the boundary: positions, counts, n_active
+            pos_h, cnt_h = host[:B], host[B:2 * B]
+            done = [b for b in range(B) if sched.slot_req[b] is not None and pos_h[b] < 0]
+            cols = hist[:, torch.tensor(done, device=dev)].t().tolist() if done else []
+            where = {b: k for k, b in enumerate(done)}
+            sched.after_chunk(n, pos_h, cnt_h, lambda b, m: cols[where[b]][:m], count_h)
+            count_h = cnt_h
+            t_steps += time.perf_counter() - t1
+        # beside the counters: host seconds spent in admission / in steps, and the position every request's slot decoded from (its group's longest prompt)
+        self.last_inflight_stats = dict(sched.stats, admission_s=t_adm, steps_s=t_steps, ctx_max=ctx_max, decode_from=[sched.decode_from[i] for i in range(sched.n)])
+        return [torch.tensor(toks, dtype=torch.int64, device=dev) for toks in sched.ordered_results()]
+
+    def _inflight_admit(self, g, reqs, sched, eos, samp_kw, uni, kv, km, st, hist, cur, count_h) -> None:
+        """One admission group through the request path of generate() as a left-padded batch (checks, vision stack, embedding splice, prefill
+        into a private cache), then into its slots: K/V rows [0, T_group), the pad holes of the key mask, the first token, the slot state."""
+        dev = self._device
+        B = sched.slots
+        rs = [reqs[i] for i in g.requests]
+        G = len(rs)
+        Tt = max(int(r["ids"].numel()) for r in rs)
+        ids = torch.zeros(G, Tt, dtype=torch.int64, device=dev)
+        am = torch.zeros(G, Tt, dtype=torch.int64, device=dev)
+        for j, r in enumerate(rs):
+            n = int(r["ids"].numel())
+            ids[j, Tt - n:] = r["ids"]
+            am[j, Tt - n:] = 1 if r["am"] is None else r["am"].to(torch.int64)
+        masked = any(r["am"] is not None or int(r["ids"].numel()) < Tt for r in rs)
+        px = torch.stack([r["px"] for r in rs]) if g.image else None
+        Q = self.config.visual_resampler_config["num_query_tokens"] if g.image else 0
+        img_pos, am2 = self._check_request(ids, am if masked else None, Q, for_generate=True)
+        img = self.embed_images(px) if px is not None else None
+        embeds, _ = self._embed(ids, img, img_pos)
+        Tg = embeds.shape[1]
+        if Tg != g.T:
+            raise ValueError(f"generate_many: group of requests {g.requests} embeds to {Tg} positions, the scheduler planned {g.T}")
+        own = self._new_cache(G, Tg)
+        logits = self._prefill(embeds, own, self._key_mask(am2, G, Tg, Tg), all_logits=False)
+        sl = torch.tensor(g.slots, device=dev)
+        kv[:, :, sl, :, :Tg, :] = own.kv
+        km[sl] = 1
+        if am2 is not None:
+            km[sl, :Tg] = am2.to(torch.int32)
+        if samp_kw is None:
+            first = _lib.argmax(logits)
+        else:                                                   # the same selector as the steps, at history length 0
+            u0 = uni[0, sl].view(1, G).contiguous() if uni is not None else None
+            first = _lib.sample(logits, _lib.sample_args(uniforms=u0, **samp_kw), n_hist=0)
+        first_h = first.tolist()                                # synchronises
+        live = []
+        for j, (i, b) in enumerate(zip(g.requests, g.slots)):
+            ended = first_h[j] in eos or sched.budget[i] == 1
+            sched.started(b, first_h[j], ended)
+            if not ended:
+                live.append((b, first_h[j], sched.budget[i]))
+        if live:
+            lb = torch.tensor([x[0] for x in live], device=dev)
+            fi = torch.tensor([x[1] for x in live], dtype=torch.int64, device=dev)
+            st[lb] = Tg                                         # row_pos
+            st[B + lb] = 1                                      # count
+            st[2 * B + lb] = 1                                  # hist_len
+            st[3 * B + lb] = torch.tensor([x[2] for x in live], dtype=torch.int32, device=dev)
+            cur[lb] = fi
+            hist[0, lb] = fi
+            for b, _, _ in live:
+                count_h[b] = 1
