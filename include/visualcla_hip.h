@@ -547,6 +547,38 @@ int vcla_slot_step(const int64_t* ids, const vcla_slot_args* args, const void* e
 int vcla_llama_decode_slots(vcla_ctx* ctx, const vcla_slot_args* slots, int n_steps, void* kv_cache, int ctx_max, const int32_t* key_mask,
                             void* ws, size_t ws_bytes, int use_graph, const vcla_sample_args* sampling, void* stream);
 
+/* ---------------------------------------------------------------- chat sessions (later turns on a kept K/V cache)
+   The reference's chat() (models/visualcla/modeling_utils.py:144-178) calls model.generate once per turn with the whole history in the
+   prompt, and every call re-runs models/visualcla/modeling_visualcla.py:349-391 over all of it: the vision stack on the same image, then
+   a prefill of every earlier instruction and response.  With a session the K/V rows of the earlier turns are still in the cache and only
+   the rows behind the common prefix are computed: a SHORT block of new rows over a LONG cache.  Additive entries; the ABI version stays 5. */
+#define VCLA_EXTEND_MAX_ROWS 256     /* longer blocks are a prefill (vcla_rope_kv_append + vcla_attention)                  */
+#define VCLA_EXTEND_QTILE_ROWS 128   /* query rows per workgroup for R > 64 (64 below: such a block is one q-tile)          */
+
+/* The attention of a block of R new rows of ONE sequence against its cache (the R-row instance of LlamaAttention.forward
+   hf:llama/modeling_llama.py:217-281): qkv [R, 3 H d] bf16 row-major at positions p .. p + R - 1 (p a host value; qkv is not modified).
+   RoPE on q and k, the R new K / V rows appended to the cache ([H][ctx_max][d] per K and V) bitwise as vcla_rope_kv_append writes
+   them, row j attends over keys [0, p + j].  out: [R, H d] row-major, or (out_frag, R <= 64) the fragment-major layout of
+   vcla_gemm_args.A_frag ([H*d/32][ceil(R/16)][64][8]).  1 <= R <= VCLA_EXTEND_MAX_ROWS, p + R <= ctx_max, d = 128 or 64, bf16 only, no
+   key mask.  The keys are cut into splits over workgroups (chosen from p + R so that a short block over a long cache fills the device);
+   scratch: vcla_attn_extend_scratch_bytes(R, H, d, p) of 16-byte aligned device memory for THAT call -- 0 when one split serves it; it
+   grows with p, so the value at the largest p a buffer will see sizes the buffer. */
+size_t vcla_attn_extend_scratch_bytes(int R, int H, int d, int p);
+int vcla_attn_extend(const void* qkv, void* k_cache, void* v_cache, const float* cos_tab, const float* sin_tab, void* out, int R, int H,
+                     int d, int ctx_max, int p, float scale, int dtype, int out_frag, void* scratch, size_t scratch_bytes, void* stream);
+
+/* Workspace of vcla_llama_extend for T rows on a cache of capacity ctx_max (the decoder rows and the attention scratch). */
+size_t vcla_llama_extend_workspace_bytes(const vcla_ctx* ctx, int T, int ctx_max);
+
+/* The decoder over T new rows of ONE sequence at positions pos0 .. pos0 + T - 1 on a cache that holds its rows [0, pos0): what
+   vcla_llama_prefill(B = 1, pos0) computes, last-position logits [1, vocab] fp32, laid out for T << pos0.  inputs_embeds [T, hidden]
+   act dtype.  bf16 with 2 <= T <= VCLA_EXTEND_MAX_ROWS and head dim 128 / 64: vcla_attn_extend, between the streaming decode GEMMs
+   (T <= 64 and fragment-major weight copies; always the bf16 values, never the fp8 decode copies) or the GEMMs a prefill of T rows
+   picks.  Otherwise (fp32, T = 1, longer blocks, head dim 32): the kernels of vcla_llama_prefill.  Not with VCLA_KV_FP8 when
+   pos0 > 0.  Replayed from a captured graph when the call repeats one (keyed on buffers, T and pos0). */
+int vcla_llama_extend(vcla_ctx* ctx, const void* inputs_embeds, int T, int pos0, void* kv_cache, int ctx_max, float* logits, void* ws,
+                      size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,389 @@
+// attention_extend.hip -- the attention of one LATER TURN of a conversation: ONE sequence, a block of R new rows at positions
+// p .. p + R - 1 (p a host value: the number of rows the session's cache already holds) over that cache, fused like vcla_attn_verify:
+//   RoPE(q), RoPE(k_new) for all R rows  ->  append the R new K / V rows to the cache  ->  row j attends over keys [0, p + j].
+//
+// The shape is a SHORT block over a LONG cache (a follow-up question is 10 - 60 tokens, the conversation hundreds to ~2000), which neither
+// existing kernel is laid out for: the causal prefill kernel (attention_mfma.hip) launches ceil(R / 128) x H workgroups -- 32 on a 256-CU
+// part at H = 32, each walking its head's whole cache alone, behind a separate RoPE / append launch -- and vcla_attn_verify stops at 16
+// rows and multiplies on the VALU.  Here:
+//   grid      (key split, q-tile, head).  A q-tile is NW waves x 32 query rows (NW = 2 up to 64 rows: such a block is ONE q-tile, so every
+//             cached row of a head is read once per pass; NW = 4 above).  The key tiles a q-tile may see, [0, p + its last row], are cut
+//             into S contiguous splits; S is chosen on the host from p + R so that the launch is about two workgroups per CU, each
+//             with at least two key tiles.
+//   products  both on v_mfma_f32_16x16x32_bf16 in the swapped form of attention_mfma.hip (S^T = K Q^T, O^T = V^T P^T: a softmax row lives
+//             in one lane column, P never moves between lanes, V^T fragments by ds_read_b64_tr_b16 from the row-major tile); online
+//             softmax per wave in the log2 domain; the next tile's rows are in flight in registers under this tile's MFMAs.
+//   new rows  keys >= p never come from the cache: the staging threads take them from `qkv` and rotate K on the way into LDS, so no
+//             workgroup reads a row another one writes.  Workgroup (split 0, q-tile 0) of each head writes the R new rows to the cache,
+//             through the same function (rope_pair: the arithmetic and roundings of vcla_rope_kv_append's bf16 kernel).
+//   merge     S = 1: the wave normalises and stores.  S > 1: per-split (o, m, l) go to scratch and attn_extend_merge_kernel combines them
+//             (attention_verify.hip's form, one more grid dimension).
+// bf16, head dim 128 or 64, no key mask (a session refuses masked prompts).
+#include "vcla_common.h"
+
+namespace {
+constexpr int XKV = 64;            // keys per tile
+constexpr int X_MAX_SPLITS = 16;
+constexpr int X_TARGET_WGS = 512;  // about two workgroups per CU of the 256-CU part
+
+// LDS images of a tile, as attention_mfma.hip lays them out: K rows with their 16-byte chunks XOR-swizzled (conflict-free ds_read_b128
+// fragments), V rows with 32-byte column blocks XOR-swizzled for the transpose reads
+template <int D> __device__ __forceinline__ int ax_k_off(int key, int ch) {
+    if (D == 128) return key * 256 + ((ch ^ (key & 15)) << 4);
+    return key * 128 + ((ch ^ ((key >> 1) & 7)) << 4);
+}
+template <int D> __device__ __forceinline__ int ax_v_off(int key, int d) {
+    constexpr int CB = D / 16;
+    const int f = D == 128 ? key : key >> 1;
+    return key * (D * 2) + ((((d >> 4) ^ f) & (CB - 1)) << 5) + ((d & 15) << 1);
+}
+typedef __attribute__((ext_vector_type(4))) short ax_s16x4_t;
+typedef __attribute__((address_space(3))) ax_s16x4_t* ax_lds_v4_t;
+
+// RoPE of 8 (x[i], x[i + d/2]) pairs at one position: bf16-rounded cos / sin, fp32 products, one rounding of each result -- the body
+// of rope_kv_vec_kernel (embed.hip), so that an appended K row is bitwise what vcla_rope_kv_append writes
+__device__ __forceinline__ void rope_pair(const uint4& lo, const uint4& hi, const float* __restrict__ cs, const float* __restrict__ sn, uint4& olo,
+                                          uint4& ohi) {
+    float c[8], s_[8], a[8], b_[8], r0[8], r1[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { c[e] = Act<bf16_t>::rnd(cs[e]); s_[e] = Act<bf16_t>::rnd(sn[e]); }
+    bf8_to_f32(lo, a); bf8_to_f32(hi, b_);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        // a c - b s and b c + a s as that kernel's compiled code forms them: one product rounded, the other fused into the sum
+        r0[e] = __builtin_fmaf(a[e], c[e], -(b_[e] * s_[e]));
+        r1[e] = __builtin_fmaf(a[e], s_[e], b_[e] * c[e]);
+    }
+    olo = make_uint4(pack_bf2(r0[0], r0[1]), pack_bf2(r0[2], r0[3]), pack_bf2(r0[4], r0[5]), pack_bf2(r0[6], r0[7]));
+    ohi = make_uint4(pack_bf2(r1[0], r1[1]), pack_bf2(r1[2], r1[3]), pack_bf2(r1[4], r1[5]), pack_bf2(r1[6], r1[7]));
+}
+__device__ __forceinline__ u32x4_t as_v4(const uint4& t) { return u32x4_t{t.x, t.y, t.z, t.w}; }
+
+// element (row m, column k) of the fragment-major layout of vcla_gemm_args.A_frag with MT 16-row tiles
+__device__ __forceinline__ int64_t ax_frag_index(int m, int k, int MT) {
+    return ((((int64_t)(k >> 5) * MT + (m >> 4)) * 64 + ((k & 31) >> 3) * 16 + (m & 15)) << 3) + (k & 7);
+}
+
+struct ExtendPlan { int nw, qb, nqt, S; };
+inline ExtendPlan extend_plan(int R, int H, int p) {
+    ExtendPlan e;
+    e.nw = R <= 64 ? 2 : 4;
+    e.qb = e.nw * 32;
+    e.nqt = (R + e.qb - 1) / e.qb;
+    const int ntiles = (p + R + XKV - 1) / XKV;
+    int S = X_TARGET_WGS / (H * e.nqt);
+    S = S < 1 ? 1 : (S > X_MAX_SPLITS ? X_MAX_SPLITS : S);
+    const int cap = ntiles / 2 > 1 ? ntiles / 2 : 1;       // at least two key tiles per split: a split's partials cost as much as a tile
+    e.S = S < cap ? S : cap;
+    return e;
+}
+}  // namespace
+
+template <int D, int NW>
+__global__ __launch_bounds__(NW * 64) void attn_extend_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ kc, bf16_t* __restrict__ vc,
+                                                              const float* __restrict__ cos_tab, const float* __restrict__ sin_tab,
+                                                              bf16_t* __restrict__ out, float* __restrict__ part, int R, int H, int ctx_max, int p,
+                                                              float scale, int out_mt) {
+    constexpr int QB = NW * 32, NT = NW * 64;
+    constexpr int HALF = D / 2;
+    constexpr int KST = D / 32;         // MFMA k-steps over the head dim (Q K^T)
+    constexpr int DT = D / 16;          // 16-wide output d tiles (P V)
+    constexpr int CH = D / 8;           // 16-byte chunks per K/V row
+    constexpr int NLD = XKV * CH / NT;  // staging loads per thread per operand
+    static_assert(XKV * CH % NT == 0, "whole staging rounds");
+    __shared__ __attribute__((aligned(16))) unsigned char lds_all[2 * XKV * D * 2];      // [K tile | V tile]
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int split = blockIdx.x, S = gridDim.x, qt_idx = blockIdx.y, nqt = gridDim.y, h = blockIdx.z;
+    const int HD = H * D;
+    const int q0 = qt_idx * QB;                  // first query row of this workgroup
+    const int qw = q0 + wave * 32;               // first query row of this wave
+    const int Tk = p + R;
+    bf16_t* kb = kc + (int64_t)h * ctx_max * D;
+    bf16_t* vb = vc + (int64_t)h * ctx_max * D;
+    const bf16_t* qh = qkv + h * D;              // row r: q at qh + r*3HD, k at + HD, v at + 2HD
+    const int ql = lane & 15, g = lane >> 4;
+    const bool wave_active = qw < R;             // waves past the end only help staging
+
+    // ---- the R new rows enter the cache: one workgroup per head writes them, none reads them back
+    if (split == 0 && qt_idx == 0) {
+        for (int idx = tid; idx < R * (CH / 2); idx += NT) {
+            const int r = idx / (CH / 2), i = (idx % (CH / 2)) * 8;
+            const bf16_t* krow = qh + (int64_t)r * 3 * HD + HD;
+            uint4 lo, hi;
+            rope_pair(*reinterpret_cast<const uint4*>(krow + i), *reinterpret_cast<const uint4*>(krow + i + HALF),
+                      cos_tab + (int64_t)(p + r) * HALF + i, sin_tab + (int64_t)(p + r) * HALF + i, lo, hi);
+            *reinterpret_cast<uint4*>(kb + (int64_t)(p + r) * D + i) = lo;
+            *reinterpret_cast<uint4*>(kb + (int64_t)(p + r) * D + i + HALF) = hi;
+        }
+        for (int idx = tid; idx < R * CH; idx += NT) {
+            const int r = idx / CH, i = (idx % CH) * 8;
+            *reinterpret_cast<uint4*>(vb + (int64_t)(p + r) * D + i) = *reinterpret_cast<const uint4*>(qh + (int64_t)r * 3 * HD + 2 * HD + i);
+        }
+    }
+
+    // ---- Q fragments (B port), rotated: lane (q = ql, g) holds Q[q][s*32 + g*8 .. +8]; the RoPE partner of chunk s is chunk s + KST/2 of
+    // the same lane
+    bf16x8_t qf[2][KST];
+#pragma unroll
+    for (int qt = 0; qt < 2; ++qt) {
+        int qr = qw + qt * 16 + ql;
+        if (qr >= R) qr = R - 1;
+        const bf16_t* qrow = qh + (int64_t)qr * 3 * HD;
+#pragma unroll
+        for (int s = 0; s < KST / 2; ++s) {
+            const int i = s * 32 + g * 8;
+            uint4 lo, hi;
+            rope_pair(*reinterpret_cast<const uint4*>(qrow + i), *reinterpret_cast<const uint4*>(qrow + i + HALF),
+                      cos_tab + (int64_t)(p + qr) * HALF + i, sin_tab + (int64_t)(p + qr) * HALF + i, lo, hi);
+            qf[qt][s] = __builtin_bit_cast(bf16x8_t, lo);
+            qf[qt][s + KST / 2] = __builtin_bit_cast(bf16x8_t, hi);
+        }
+    }
+
+    f32x4_t o[2][DT];
+#pragma unroll
+    for (int qt = 0; qt < 2; ++qt)
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt) o[qt][dt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    float m_run[2] = {-INFINITY, -INFINITY}, l_run[2] = {0.f, 0.f};
+    const float sl2 = scale * 1.44269504088896340736f;  // scores are kept in the log2 domain
+
+    // ---- this split's share of the key tiles the q-tile may see (causal: up to its last row)
+    const int last_q = (q0 + QB < R ? q0 + QB : R) - 1;
+    const int kv_end = p + last_q + 1;
+    const int ntiles = (kv_end + XKV - 1) / XKV;
+    const int per = (ntiles + S - 1) / S;
+    const int t_lo = split * per, t_hi = t_lo + per < ntiles ? t_lo + per : ntiles;
+
+    // ---- staging: cached rows from the cache, new rows (keys >= p) from qkv with K rotated on the way
+    u32x4_t rk[NLD], rv[NLD];
+    auto load_tile = [&](int tile) {
+#pragma unroll
+        for (int i = 0; i < NLD; ++i) {
+            const int id = i * NT + tid, key = id / CH, ch = id % CH;
+            int kg = tile * XKV + key;
+            if (kg >= Tk) kg = Tk - 1;           // clamp; masked below
+            if (kg < p) {
+                rk[i] = *reinterpret_cast<const u32x4_t*>(kb + (int64_t)kg * D + ch * 8);
+                rv[i] = *reinterpret_cast<const u32x4_t*>(vb + (int64_t)kg * D + ch * 8);
+            } else {
+                const bf16_t* row = qh + (int64_t)(kg - p) * 3 * HD;
+                const int cl = (ch % (CH / 2)) * 8;
+                uint4 lo, hi;
+                rope_pair(*reinterpret_cast<const uint4*>(row + HD + cl), *reinterpret_cast<const uint4*>(row + HD + cl + HALF),
+                          cos_tab + (int64_t)kg * HALF + cl, sin_tab + (int64_t)kg * HALF + cl, lo, hi);
+                rk[i] = ch < CH / 2 ? as_v4(lo) : as_v4(hi);
+                rv[i] = *reinterpret_cast<const u32x4_t*>(row + 2 * HD + ch * 8);
+            }
+        }
+    };
+    auto store_tile = [&]() {
+#pragma unroll
+        for (int i = 0; i < NLD; ++i) {
+            const int id = i * NT + tid, key = id / CH, ch = id % CH;
+            *reinterpret_cast<u32x4_t*>(lds_all + ax_k_off<D>(key, ch)) = rk[i];
+            *reinterpret_cast<u32x4_t*>(lds_all + XKV * D * 2 + ax_v_off<D>(key, ch * 8)) = rv[i];
+        }
+    };
+
+    // ---- one key tile of 64 keys against the wave's 32 query rows
+    auto tile_body = [&](int kv0) {
+        constexpr int NTK = 4, NS = 2;
+        const unsigned char* ks = lds_all;
+        const auto v_lds = (__attribute__((address_space(3))) unsigned char*)lds_all + XKV * D * 2;
+        f32x4_t sacc[2][NTK];
+#pragma unroll
+        for (int qt = 0; qt < 2; ++qt)
+#pragma unroll
+            for (int t = 0; t < NTK; ++t) sacc[qt][t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int s = 0; s < KST; ++s) {
+#pragma unroll
+            for (int t = 0; t < NTK; ++t) {
+                const bf16x8_t kf = *reinterpret_cast<const bf16x8_t*>(ks + ax_k_off<D>(t * 16 + ql, s * 4 + g));
+                sacc[0][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[0][s], sacc[0][t], 0, 0, 0);
+                sacc[1][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[1][s], sacc[1][t], 0, 0, 0);
+            }
+        }
+        // lane holds keys kv0 + t*16 + g*4 + r of query rows qw + qt*16 + ql; row j sees keys <= p + j (wave-uniform test first)
+        if (kv0 + XKV - 1 > qw + p) {
+#pragma unroll
+            for (int qt = 0; qt < 2; ++qt) {
+                const int klim = p + qw + qt * 16 + ql;          // last visible key (rows >= R are never stored)
+#pragma unroll
+                for (int t = 0; t < NTK; ++t)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int key = kv0 + t * 16 + g * 4 + r;
+                        sacc[qt][t][r] = (key <= klim && key < Tk) ? sacc[qt][t][r] : -INFINITY;
+                    }
+            }
+        }
+        bf16x8_t pf[2][NS];
+#pragma unroll
+        for (int qt = 0; qt < 2; ++qt) {
+            float mx = -INFINITY;
+#pragma unroll
+            for (int t = 0; t < NTK; ++t)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) mx = fmaxf(mx, sacc[qt][t][r]);
+            mx *= sl2;                                   // log2 domain (-inf stays -inf)
+            mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+            const float m_new = fmaxf(m_run[qt], mx);
+            const float m_use = (m_new == -INFINITY) ? 0.f : m_new;  // nothing visible so far: keep everything at 0
+            const float alpha = exp2f(m_run[qt] - m_use);             // exp2(-inf) = 0 on the first tile
+            m_run[qt] = m_new;
+            float ps = 0.f;
+            float pv[NTK * 4];
+#pragma unroll
+            for (int t = 0; t < NTK; ++t)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float pp = __builtin_amdgcn_exp2f(__builtin_fmaf(sacc[qt][t][r], sl2, -m_use));
+                    pv[t * 4 + r] = pp;
+                    ps += pp;
+                }
+            l_run[qt] = l_run[qt] * alpha + ps;
+#pragma unroll
+            for (int dt = 0; dt < DT; ++dt) o[qt][dt] *= alpha;
+            // P^T fragments: key-step s takes S tiles (2s, 2s+1): slots j<4 from tile 2s, j>=4 from tile 2s+1
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {
+                uint4 u;
+                u.x = pack_bf2(pv[(2 * s) * 4 + 0], pv[(2 * s) * 4 + 1]);
+                u.y = pack_bf2(pv[(2 * s) * 4 + 2], pv[(2 * s) * 4 + 3]);
+                u.z = pack_bf2(pv[(2 * s + 1) * 4 + 0], pv[(2 * s + 1) * 4 + 1]);
+                u.w = pack_bf2(pv[(2 * s + 1) * 4 + 2], pv[(2 * s + 1) * 4 + 3]);
+                pf[qt][s] = __builtin_bit_cast(bf16x8_t, u);
+            }
+        }
+        // ---- O^T += V^T P^T
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt) {
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {
+                // lane (ql, g): piece (key row ql / 4, 8 bytes ql % 4) of the 4-key x 16-d blocks of S tiles 2s and 2s + 1
+                const int kr = g * 4 + (ql >> 2), dc = dt * 16 + (ql & 3) * 4;
+                const ax_s16x4_t v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ax_lds_v4_t)(v_lds + ax_v_off<D>((2 * s) * 16 + kr, dc)));
+                const ax_s16x4_t v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ax_lds_v4_t)(v_lds + ax_v_off<D>((2 * s + 1) * 16 + kr, dc)));
+                const bf16x8_t vf = __builtin_bit_cast(bf16x8_t, __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7));
+                o[0][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[0][s], o[0][dt], 0, 0, 0);
+                o[1][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[1][s], o[1][dt], 0, 0, 0);
+            }
+        }
+    };
+
+    if (t_lo < t_hi) load_tile(t_lo);
+    for (int tile = t_lo; tile < t_hi; ++tile) {
+        __syncthreads();          // previous tile fully consumed
+        store_tile();
+        __syncthreads();
+        load_tile(tile + 1 < t_hi ? tile + 1 : tile);      // unconditional (the last one is a harmless re-load): keeps the prefetch
+                                                           // registers out of the private segment
+        const int kv0 = tile * XKV;
+        // a wave whose rows all precede this tile has nothing to do here
+        if (wave_active && kv0 <= (qw + 31 < R ? qw + 31 : R - 1) + p) tile_body(kv0);
+    }
+    if (!wave_active) return;
+
+    // ---- epilogue: lane holds d = dt*16 + g*4 + r of query row qw + qt*16 + ql
+#pragma unroll
+    for (int qt = 0; qt < 2; ++qt) {
+        float l = l_run[qt];
+        l += __shfl_xor(l, 16, 64);
+        l += __shfl_xor(l, 32, 64);
+        const int qrow = qw + qt * 16 + ql;
+        if (qrow >= R) continue;
+        if (S == 1) {
+            const float inv = l > 0.f ? 1.0f / l : 0.f;
+#pragma unroll
+            for (int dt = 0; dt < DT; ++dt) {
+                float v[4] = {o[qt][dt][0] * inv, o[qt][dt][1] * inv, o[qt][dt][2] * inv, o[qt][dt][3] * inv};
+                const int k = h * D + dt * 16 + g * 4;
+                Act<bf16_t>::st4(out_mt > 0 ? out + ax_frag_index(qrow, k, out_mt) : out + (int64_t)qrow * HD + k, v);
+            }
+        } else {
+            float* pw = part + ((((int64_t)h * nqt + qt_idx) * S + split) * QB + (qrow - q0)) * (D + 4);
+#pragma unroll
+            for (int dt = 0; dt < DT; ++dt) *reinterpret_cast<f32x4_t*>(pw + dt * 16 + g * 4) = o[qt][dt];
+            if (g == 0) { pw[D] = m_run[qt]; pw[D + 1] = l; }
+        }
+    }
+}
+
+// S > 1: out[r, h, :] = sum_s o_s 2^(m_s - m) / sum_s l_s 2^(m_s - m).  A thread owns 4 consecutive d of one row, a workgroup 256 / (D / 4)
+// rows of one head: the grid is as wide as the block has rows, so the partials are read at the device's rate, not at 32 workgroups'
+template <int D>
+__global__ __launch_bounds__(256) void attn_extend_merge_kernel(const float* __restrict__ part, bf16_t* __restrict__ out, int R, int H, int S, int QB,
+                                                               int nqt, int out_mt) {
+    constexpr int LPR = D / 4, RPB = 256 / LPR;              // lanes per row, rows per workgroup
+    const int h = blockIdx.y, row = blockIdx.x * RPB + threadIdx.x / LPR, dd = (threadIdx.x % LPR) * 4;
+    if (row >= R) return;
+    const int qt_idx = row / QB, r = row % QB;
+    const float* base = part + ((((int64_t)h * nqt + qt_idx) * S) * QB + r) * (D + 4);
+    const int64_t ss = (int64_t)QB * (D + 4);                // stride between the splits of one row
+    float mf = -INFINITY;
+    for (int s = 0; s < S; ++s) mf = fmaxf(mf, base[s * ss + D]);
+    const float mu = mf == -INFINITY ? 0.f : mf;
+    float lf = 0.f;
+    f32x4_t of = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+    for (int s = 0; s < S; ++s) {
+        const float* pw = base + s * ss;
+        const float a = exp2f(pw[D] - mu);
+        lf += pw[D + 1] * a;
+        of += *reinterpret_cast<const f32x4_t*>(pw + dd) * a;
+    }
+    const float inv = lf > 0.f ? 1.0f / lf : 0.f;
+    float v[4] = {of[0] * inv, of[1] * inv, of[2] * inv, of[3] * inv};
+    const int k = h * D + dd;
+    Act<bf16_t>::st4(out_mt > 0 ? out + ax_frag_index(row, k, out_mt) : out + (int64_t)row * H * D + k, v);
+}
+
+extern "C" size_t vcla_attn_extend_scratch_bytes(int R, int H, int d, int p) {
+    if (R <= 0 || R > VCLA_EXTEND_MAX_ROWS || H <= 0 || d <= 0 || p < 0) return 0;
+    const ExtendPlan e = extend_plan(R, H, p);
+    return e.S > 1 ? (size_t)H * e.nqt * e.S * e.qb * (d + 4) * sizeof(float) : 0;
+}
+
+template <int D, int NW>
+static int launch_extend(const void* qkv, void* kc, void* vc, const float* cos_tab, const float* sin_tab, void* out, int R, int H, int ctx_max, int p,
+                         float scale, int out_mt, const ExtendPlan& e, float* scratch, hipStream_t s) {
+    attn_extend_kernel<D, NW><<<dim3(e.S, e.nqt, H), NW * 64, 0, s>>>((const bf16_t*)qkv, (bf16_t*)kc, (bf16_t*)vc, cos_tab, sin_tab, (bf16_t*)out,
+                                                                     scratch, R, H, ctx_max, p, scale, out_mt);
+    VCLA_CHECK_LAUNCH("attn_extend_kernel");
+    if (e.S > 1) {
+        constexpr int RPB = 256 / (D / 4);
+        attn_extend_merge_kernel<D><<<dim3((R + RPB - 1) / RPB, H), 256, 0, s>>>(scratch, (bf16_t*)out, R, H, e.S, e.qb, e.nqt, out_mt);
+        VCLA_CHECK_LAUNCH("attn_extend_merge_kernel");
+    }
+    return VCLA_OK;
+}
+
+extern "C" int vcla_attn_extend(const void* qkv, void* k_cache, void* v_cache, const float* cos_tab, const float* sin_tab, void* out, int R, int H,
+                                int d, int ctx_max, int p, float scale, int dtype, int out_frag, void* scratch, size_t scratch_bytes, void* stream) {
+    VCLA_REQUIRE(dtype == VCLA_BF16, VCLA_ERR_BAD_DTYPE, "attn_extend: bad dtype %d (bf16 rows and a bf16 cache only)", dtype);
+    VCLA_REQUIRE(d == 64 || d == 128, VCLA_ERR_BAD_SHAPE, "attn_extend: head dim %d not in {64,128}", d);
+    VCLA_REQUIRE(R >= 1 && R <= VCLA_EXTEND_MAX_ROWS && H > 0 && ctx_max > 0 && p >= 0 && p + R <= ctx_max, VCLA_ERR_BAD_SHAPE,
+                 "attn_extend: R=%d (1..%d) H=%d ctx_max=%d p=%d", R, VCLA_EXTEND_MAX_ROWS, H, ctx_max, p);
+    VCLA_REQUIRE(qkv && k_cache && v_cache && cos_tab && sin_tab && out, VCLA_ERR_BAD_ARG, "attn_extend: null pointer");
+    VCLA_REQUIRE(vcla_aligned(qkv, 16) && vcla_aligned(k_cache, 16) && vcla_aligned(v_cache, 16) && vcla_aligned(out, 16), VCLA_ERR_BAD_ARG,
+                 "attn_extend: qkv, the caches and out must be 16-byte aligned");
+    VCLA_REQUIRE(!out_frag || (R <= 64 && (H * d) % 32 == 0), VCLA_ERR_BAD_ARG, "attn_extend: out_frag needs R <= 64 (got %d) and H*d %% 32 == 0", R);
+    const ExtendPlan e = extend_plan(R, H, p);
+    const size_t need = vcla_attn_extend_scratch_bytes(R, H, d, p);
+    VCLA_REQUIRE(scratch_bytes >= need && (need == 0 || (scratch && vcla_aligned(scratch, 16))), VCLA_ERR_WORKSPACE,
+                 "attn_extend: scratch %zu < %zu bytes", scratch_bytes, need);
+    const int out_mt = out_frag ? (R + 15) / 16 : 0;
+    hipStream_t s = (hipStream_t)stream;
+#define XT_CASE(DD, NN) return launch_extend<DD, NN>(qkv, k_cache, v_cache, cos_tab, sin_tab, out, R, H, ctx_max, p, scale, out_mt, e, (float*)scratch, s)
+    if (d == 64) {
+        if (e.nw == 2) XT_CASE(64, 2);
+        XT_CASE(64, 4);
+    }
+    if (e.nw == 2) XT_CASE(128, 2);
+    XT_CASE(128, 4);
+#undef XT_CASE
+}

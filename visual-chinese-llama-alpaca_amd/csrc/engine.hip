@@ -188,6 +188,9 @@ struct vcla_ctx {
         bool verify = false;           // inside verify_iter_impl: the T rows of llama_layer are one sequence's verify rows (vcla_attn_verify)
         void* verify_scratch = nullptr;
         size_t verify_scratch_bytes = 0;
+        bool extend = false;           // inside vcla_llama_extend with a block vcla_attn_extend takes: the T rows of llama_layer are one sequence's new rows at pos0
+        void* extend_scratch = nullptr;
+        size_t extend_scratch_bytes = 0;
     } run;
     // cached graphs of the vision stack and of the prefill (~250 / ~290 launches, host-bound at B = 1; run_macro), two shapes in rotation
     // each (e.g. forward(all_logits) and generate()'s prefill, or two batch sizes); of one decode step and of one verify iteration
@@ -781,11 +784,13 @@ static int vision_forward_impl(vcla_ctx* ctx, const void* pixel_values, void* im
 // M rows go to the GEMV kernel, which applies the RMSNorm in its prologue (norm_gamma): must mirror vcla_gemm's kernel choice.
 static bool gemv_norm(int dt, int M) { return (dt == VCLA_F32) ? (M <= 8) : (M == 1); }
 
-// 2 <= M <= 64 rows of a decode step (T = 1) or a verify iteration run the streaming decode GEMMs (gemm_stream.hip).  The final norm +
-// lm_head asks the same question: it consumes w.h / w.ssq in the layout these layers leave behind.
+// 2 <= M <= 64 rows of a decode step (T = 1), a verify iteration or a session's new block (vcla_llama_extend) run the streaming decode
+// GEMMs (gemm_stream.hip).  The final norm + lm_head of decoder_rows asks the same question: it consumes w.h / w.ssq in the layout these
+// layers leave behind.
 static bool stream_layers(const vcla_ctx* ctx, int M, int T) {
     const vcla_model_cfg& c = ctx->c;
-    return vcla_knobs_get().dstream && ctx->run.decode_step && (T == 1 || ctx->run.verify) && c.act_dtype == VCLA_BF16 && M >= 2 && M <= 64 &&
+    const bool rows = (ctx->run.decode_step && (T == 1 || ctx->run.verify)) || ctx->run.extend;
+    return vcla_knobs_get().dstream && rows && c.act_dtype == VCLA_BF16 && M >= 2 && M <= 64 &&
            ctx->twins_complete && c.t_hidden % 32 == 0 && c.t_inter % 32 == 0;
 }
 
@@ -807,9 +812,10 @@ static int llama_layer(vcla_ctx* ctx, hipStream_t s, const LlamaLayer& L, const 
     // the SwiGLU epilogue stores the activations that way; the residual stream w.x stays row-major.  7 launches per layer,
     // no split-K partials.
     const vcla_knobs& kn = vcla_knobs_get();
-    // Decode steps only (ctx->run.decode_step): the branch leaves w.h fragment-major and un-normalised, which decoder_rows'
-    // final norm + lm_head expect and vcla_llama_prefill's all_logits tail (row-major w.h) does not -- a single-token
-    // forward(input_ids[B, 1], past_key_values=cache) goes through the panel kernels below.
+    // Decode steps (ctx->run.decode_step) and a session's new block (ctx->run.extend) only: the branch leaves w.h fragment-major and
+    // un-normalised, which decoder_rows' final norm + lm_head expect and vcla_llama_prefill's all_logits tail (row-major w.h) does not
+    // -- a single-token forward(input_ids[B, 1], past_key_values=cache) goes through the panel kernels below.  vcla_llama_extend
+    // reads only the residual stream w.x behind the layers, which stays row-major.
     const bool verify = ctx->run.verify;   // B = 1, T = k + 1 verify rows at pos0 + *pos_dev (vcla_llama_verify_loop)
     if (stream_layers(ctx, M, T)) {
         // RMSNorm is deferred across the GEMMs (VCLA_DS_DEFER=0: a vcla_rmsnorm_pack launch per norm instead): o_proj / down_proj
@@ -836,6 +842,12 @@ static int llama_layer(vcla_ctx* ctx, hipStream_t s, const LlamaLayer& L, const 
                         a_def ? w.ssq : nullptr, a_def ? ctx->run.ssq_parts : 0));
             RUN(vcla_attn_decode_rows(w.qkv, kc, vc, ctx->rope_cos, ctx->rope_sin, w.ao, B, H, d, ctx_max, row_pos, key_mask, ctx_max, scale_, dt,
                                       /*out_frag=*/1, s));
+        } else if (ctx->run.extend) {
+            // a session's new block: the T rows of one sequence at pos0 .. over its cached rows [0, pos0)
+            RUN(gemm_ds(ctx, s, w.h, L.wqkv, L.vqkv, nullptr, 0, w.qkv, 3 * D, nullptr, M, 3 * D, D, VCLA_EPI_NONE, 0,
+                        a_def ? w.ssq : nullptr, a_def ? ctx->run.ssq_parts : 0));
+            RUN(vcla_attn_extend(w.qkv, kc, vc, ctx->rope_cos, ctx->rope_sin, w.ao, T, H, d, ctx_max, pos0, scale_, dt, /*out_frag=*/1,
+                                 ctx->run.extend_scratch, ctx->run.extend_scratch_bytes, s));
         } else if (verify) {
             RUN(gemm_ds(ctx, s, w.h, L.wqkv, L.vqkv, nullptr, 0, w.qkv, 3 * D, nullptr, M, 3 * D, D, VCLA_EPI_NONE, 0,
                         a_def ? w.ssq : nullptr, a_def ? ctx->run.ssq_parts : 0));
@@ -883,6 +895,10 @@ static int llama_layer(vcla_ctx* ctx, hipStream_t s, const LlamaLayer& L, const 
         // verify rows: RoPE + KV append + causal attention over the cache, position from pos_dev
         RUN(vcla_attn_verify(w.qkv, kc, vc, ctx->rope_cos, ctx->rope_sin, w.ao, T, H, d, ctx_max, pos0, pos_dev, key_mask, scale, dkv, 0,
                              ctx->run.verify_scratch, ctx->run.verify_scratch_bytes, s));
+    } else if (ctx->run.extend) {
+        // a session's new block: RoPE + KV append + causal attention over the cache in one launch, keys split over workgroups
+        RUN(vcla_attn_extend(w.qkv, kc, vc, ctx->rope_cos, ctx->rope_sin, w.ao, T, H, d, ctx_max, pos0, scale, dt, 0, ctx->run.extend_scratch,
+                             ctx->run.extend_scratch_bytes, s));
     } else if (T == 1 && row_pos) {
         // a slots step: the same launch with one position per row
         RUN(vcla_attn_decode_rows(w.qkv, kc, vc, ctx->rope_cos, ctx->rope_sin, w.ao, B, H, d, ctx_max, row_pos, key_mask, ctx_max, scale, dt, 0, s));
@@ -1006,6 +1022,62 @@ static int llama_prefill_impl(vcla_ctx* ctx, const void* inputs_embeds, int B, i
         RUN(gemm(ctx, s, w.hl, D, ctx->lm_head, nullptr, nullptr, 0, logits, c.t_vocab, B, c.t_vocab, D, VCLA_EPI_NONE, 1));
     }
     return VCLA_OK;
+}
+
+// ------------------------------------------------------------------ a session's later turn: T new rows of one sequence on its kept cache
+// What vcla_llama_prefill(B = 1, pos0) computes, for a SHORT block over a LONG cache.  llama_layer in its `extend` mode: vcla_attn_extend
+// (RoPE + append + attention in one launch, keys split over workgroups) between the streaming decode GEMMs for T <= 64 or the GEMMs a
+// prefill of T rows picks.  Blocks the kernel does not take (fp32, T = 1, T > VCLA_EXTEND_MAX_ROWS, head dim 32) run llama_layer as the
+// prefill does.  No graph: (T, pos0) of a conversation's turns do not repeat.
+static bool extend_kernel_ok(const vcla_ctx* ctx, int T) {
+    const vcla_model_cfg& c = ctx->c;
+    const int d = c.t_hidden / c.t_heads;
+    return c.act_dtype == VCLA_BF16 && !c.t_kv_fp8 && T >= 2 && T <= VCLA_EXTEND_MAX_ROWS && (d == 128 || d == 64);
+}
+static size_t carve_extend(const vcla_ctx* ctx, int T, int ctx_max, char* base, LlamaWs* w, void** scratch, size_t* scratch_bytes) {
+    const size_t lw = carve_llama(ctx, 1, T, base, w);
+    // the split scratch grows with the start position: sized for the last one this cache admits
+    const size_t sb = extend_kernel_ok(ctx, T) && ctx_max >= T ? vcla_attn_extend_scratch_bytes(T, ctx->c.t_heads, ctx->c.t_hidden / ctx->c.t_heads, ctx_max - T) : 0;
+    const size_t off = (lw + 255) & ~(size_t)255;
+    if (scratch) *scratch = (base && sb) ? base + off : nullptr;
+    if (scratch_bytes) *scratch_bytes = sb;
+    return off + sb + 256;
+}
+extern "C" size_t vcla_llama_extend_workspace_bytes(const vcla_ctx* ctx, int T, int ctx_max) {
+    if (!ctx || T <= 0 || ctx_max <= 0 || ctx->c.t_layers <= 0) return 0;
+    return carve_extend(ctx, T, ctx_max, nullptr, nullptr, nullptr, nullptr);
+}
+
+extern "C" int vcla_llama_extend(vcla_ctx* ctx, const void* inputs_embeds, int T, int pos0, void* kv_cache, int ctx_max, float* logits, void* ws,
+                                 size_t ws_bytes, void* stream) {
+    VCLA_KNOBS_SCOPE();
+    VCLA_REQUIRE(ctx && ctx->finalized && ctx->c.t_layers > 0, VCLA_ERR_BAD_ARG, "llama_extend: context not finalized, or vision-only");
+    VCLA_REQUIRE(inputs_embeds && kv_cache && logits && ws, VCLA_ERR_BAD_ARG, "llama_extend: null pointer");
+    const vcla_model_cfg& c = ctx->c;
+    VCLA_REQUIRE(T > 0 && pos0 >= 0 && pos0 + T <= ctx_max && ctx_max <= c.t_max_pos, VCLA_ERR_BAD_SHAPE,
+                 "llama_extend: T=%d pos0=%d ctx_max=%d (max_pos %d)", T, pos0, ctx_max, c.t_max_pos);
+    VCLA_REQUIRE(!(c.t_kv_fp8 && pos0 > 0), VCLA_ERR_BAD_ARG, "llama_extend: the e4m3 K/V cache is not supported behind position 0 -- nothing was written");
+    VCLA_REQUIRE(ws_bytes >= vcla_llama_extend_workspace_bytes(ctx, T, ctx_max), VCLA_ERR_WORKSPACE, "llama_extend: workspace %zu < %zu bytes", ws_bytes,
+                 vcla_llama_extend_workspace_bytes(ctx, T, ctx_max));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t e = esz(ctx);
+    const int D = c.t_hidden;
+    LlamaWs w;
+    void* scratch = nullptr;
+    size_t scratch_bytes = 0;
+    carve_extend(ctx, T, ctx_max, align256(ws), &w, &scratch, &scratch_bytes);
+    ctx->run.splitk_ws = w.splitk;
+    const RunScope scope(ctx);
+    ctx->run.q8_ws = w.q8; ctx->run.q8s_ws = w.q8s;
+    ctx->run.extend = extend_kernel_ok(ctx, T);
+    ctx->run.extend_scratch = scratch;
+    ctx->run.extend_scratch_bytes = scratch_bytes;
+    VCLA_CHECK_HIP(hipMemcpyAsync(w.x, inputs_embeds, (size_t)T * D * e, hipMemcpyDeviceToDevice, s));
+    for (int l = 0; l < c.t_layers; ++l)
+        RUN(llama_layer(ctx, s, ctx->llama[l], w, l, 1, T, pos0, nullptr, kv_cache, ctx_max, nullptr, l > 0, l + 1 < c.t_layers ? ctx->llama[l + 1].ln1g : nullptr));
+    // the last row only; every route leaves the residual stream row-major in w.x
+    RUN(vcla_rmsnorm((char*)w.x + (size_t)(T - 1) * D * e, D, ctx->norm_g, w.hl, D, 1, D, c.t_eps, c.act_dtype, s));
+    return gemm(ctx, s, w.hl, D, ctx->lm_head, nullptr, nullptr, 0, logits, c.t_vocab, 1, c.t_vocab, D, VCLA_EPI_NONE, 1);
 }
 
 // The persistent decode step serves B = 1 in the bf16 mode when its weight stream is registered, no fp8 decode copies are loaded (those

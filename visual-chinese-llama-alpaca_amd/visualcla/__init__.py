@@ -3,6 +3,7 @@ same exported names, arithmetic executed by libvisualcla_hip.so (hand-written gf
 from .configuration_visualcla import VisualCLAConfig, visualcla_7b_config
 from .modeling_visualcla import VisualCLAModel
 from .processing_visualcla import VisualCLAProcessor
+from .session import Session
 from .modeling_utils import (
     DEFAULT_GENERATION_CONFIG,
     chat,
@@ -16,5 +17,5 @@ from .modeling_utils import (
 __all__ = [
     "VisualCLAModel", "VisualCLAConfig", "VisualCLAProcessor", "get_model_and_tokenizer_and_processor",
     "get_model_and_processor", "chat", "chat_many", "chat_in_stream", "hijack_samplers", "DEFAULT_GENERATION_CONFIG",
-    "visualcla_7b_config",
+    "visualcla_7b_config", "Session",
 ]

@@ -135,6 +135,9 @@ def lookup_args(k, ngram_max, budget, eos_ids, row, history, out, state, filler=
     return a
 
 
+EXTEND_MAX_ROWS = 256       # VCLA_EXTEND_MAX_ROWS: new rows of a session's turn vcla_attn_extend takes (longer blocks are a prefill)
+EXTEND_QTILE_ROWS = 128     # VCLA_EXTEND_QTILE_ROWS: query rows per workgroup above 64 rows
+
 SLOT_MAX_EOS = 8            # VCLA_SLOT_MAX_EOS
 SLOT_SUMMARY_WORDS = 4      # VCLA_SLOT_SUMMARY_WORDS: slots still active, the launch's arrival counter, two reserved words
 
@@ -210,6 +213,10 @@ SYMBOLS = {
     "vcla_sample_rows": (_i, [_vp, _i64, _i, _i, _vp, C.POINTER(SampleArgs), _vp, _vp]),
     "vcla_slot_step": (_i, [_vp, C.POINTER(SlotArgs), _vp, _vp, _i, _i, _i, _vp]),
     "vcla_llama_decode_slots": (_i, [_vp, C.POINTER(SlotArgs), _i, _vp, _i, _vp, _vp, _sz, _i, C.POINTER(SampleArgs), _vp]),
+    "vcla_attn_extend_scratch_bytes": (_sz, [_i, _i, _i, _i]),
+    "vcla_attn_extend": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _i, _vp, _sz, _vp]),
+    "vcla_llama_extend_workspace_bytes": (_sz, [_vp, _i, _i]),
+    "vcla_llama_extend": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _sz, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -151,11 +151,14 @@ def _prepare(model, image, text, history, generation_config):
 
 
 @torch.inference_mode()
-def chat(model, image: Union[str, "Image.Image", torch.Tensor], text: str, history=[], generation_config=None):
-    """-> (response, history); appends to / mutates the caller's `history` and prints both, as the reference does."""
+def chat(model, image: Union[str, "Image.Image", torch.Tensor], text: str, history=[], generation_config=None, session=None):
+    """-> (response, history); appends to / mutates the caller's `history` and prints both, as the reference does.
+    session (model.new_session(), not in the reference): the K/V rows of the earlier turns are kept in it, so a later turn computes only its
+    new tokens; the prompt, the response and the history are those of the call without it."""
     generation_config, enc = _prepare(model, image, text, history, generation_config)
+    extra = {} if session is None else {"session": session}
     outputs = model.generate(input_ids=enc.input_ids, attention_mask=enc.attention_mask,
-                             pixel_values=enc.pixel_values, generation_config=generation_config)
+                             pixel_values=enc.pixel_values, generation_config=generation_config, **extra)
     response = model.tokenizer.decode(outputs[0], skip_special_tokens=True)
     history.append({"type": "response", "value": response})
     print("Response:", response)
@@ -189,9 +192,9 @@ def chat_many(model, items, generation_config=None, max_batch=64):
 
 
 @torch.inference_mode()
-def chat_in_stream(model, image: Union[str, "Image.Image", torch.Tensor], text: str, history=[], generation_config=None):
+def chat_in_stream(model, image: Union[str, "Image.Image", torch.Tensor], text: str, history=[], generation_config=None, session=None):
     """Generator of (response_so_far, history).  generate() runs in a worker thread and hands the growing id
-    sequence over a queue from a per-token stopping-criteria callback (reference :215-225, :404-472)."""
+    sequence over a queue from a per-token stopping-criteria callback (reference :215-225, :404-472).  session: as chat()."""
     from transformers import LlamaTokenizer
     generation_config, enc = _prepare(model, image, text, history, generation_config)
     origin_size = len(enc.input_ids[0])
@@ -205,6 +208,8 @@ def chat_in_stream(model, image: Union[str, "Image.Image", torch.Tensor], text: 
     params["input_ids"] = enc.input_ids
     params["attention_mask"] = enc.attention_mask
     params["pixel_values"] = enc.pixel_values
+    if session is not None:
+        params["session"] = session
 
     def generate_with_callback(callback=None, **kw):
         kw.setdefault("stopping_criteria", [])

@@ -128,6 +128,7 @@ class VisualCLAModel:
             _lib.check(lib.vcla_ctx_set_tensor(self._ctx, name.encode(), t.data_ptr(), t.numel() * t.element_size()))
         _lib.check(lib.vcla_ctx_finalize(self._ctx))
         self._pos_dev = torch.zeros(1, dtype=torch.int32, device=self._device)
+        self._session_epoch = getattr(self, "_session_epoch", 0) + 1     # a rebuilt context (dtype, fp8 switches, image size) empties live sessions
 
     def _destroy_ctx(self) -> None:
         if getattr(self, "_ctx", None):
@@ -607,6 +608,30 @@ class VisualCLAModel:
             taps["logits"] = logits
         return logits
 
+    def _extend(self, embeds: torch.Tensor, cache: VclaCache, _persistent: bool = False):
+        """the decoder over the new rows [1, Tn, D] of ONE sequence on a cache that holds its rows [0, cache.length) -> last-position logits
+        [1, V] (vcla_llama_extend: a short block over a long cache)"""
+        lib = _lib.load()
+        _, Tn, _ = embeds.shape
+        V = self.config.text_config["vocab_size"]
+        pos0 = cache.length
+        if pos0 + Tn > cache.ctx_max:
+            raise ValueError(f"sequence length {pos0 + Tn} exceeds the KV cache capacity {cache.ctx_max}")
+        logits = self._typed_buf("gen_logits", (1, V), torch.float32) if _persistent else torch.empty(1, V, dtype=torch.float32, device=self._device)
+        ws = self._buf("extend", lib.vcla_llama_extend_workspace_bytes(self._ctx, Tn, cache.ctx_max))
+        embeds = embeds.contiguous()
+        with torch.cuda.device(self._device):
+            _lib.check(lib.vcla_llama_extend(self._ctx, embeds.data_ptr(), Tn, pos0, cache.kv.data_ptr(), cache.ctx_max, logits.data_ptr(),
+                                             ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
+        cache.length = pos0 + Tn
+        return logits
+
+    def new_session(self, max_tokens: Optional[int] = None):
+        """-> visualcla.session.Session: the K/V rows of one conversation, kept between generate(session=) / chat(session=) calls.  Its
+        buffer holds `max_tokens` positions (default max_position_embeddings: 1 GiB at the 7B shape in bf16, `session.nbytes`)."""
+        from .session import Session
+        return Session(self, max_tokens)
+
     def _check_decode_status(self, B: int, ws: torch.Tensor) -> None:
         """At B = 1 the decode steps of the bf16 mode are persistent launches whose workgroups wait on each other with BOUNDED spins
         (csrc/decode_engine.hip); a wait that ran out leaves a code in the workspace and the tokens are garbage -- raise instead of returning
@@ -722,14 +747,18 @@ class VisualCLAModel:
     @torch.no_grad()
     def generate(self, input_ids=None, pixel_values=None, attention_mask=None, generation_config=None,
                  logits_processor=None, stopping_criteria=None, prefix_allowed_tokens_fn=None, synced_gpus=False,
-                 use_graph: Optional[bool] = None, device_sampling: Optional[bool] = None, **kwargs):
+                 use_graph: Optional[bool] = None, device_sampling: Optional[bool] = None, session=None, **kwargs):
         """Same contract as the reference generate (modeling_visualcla.py:334-392): returns the NEW tokens only,
         LongTensor [B, n_new] (what HF generate returns when driven by inputs_embeds).  Greedy decoding without
         callbacks runs entirely on the device (argmax feeds the next step; optional hipGraph replay); so does sampling /
         greedy with HF's standard processors (repetition penalty, no-repeat-ngram, min-new-tokens, temperature, top-k <= 256,
         top-p) through vcla_sample, drawing from torch.rand(n_new, B) of the device generator.  Custom logits processors,
         stopping criteria (streaming), `prefix_allowed_tokens_fn` or top_k = 0 take the host-driven path (HF processors +
-        torch.multinomial)."""
+        torch.multinomial).
+
+        session (model.new_session()): a cache, not another protocol -- `input_ids` is still the FULL prompt and the tokens are those of the
+        same call without a session; only the rows behind the common prefix of the prompt and the session's ids are computed, and the
+        vision stack is skipped when the image slot lies inside that prefix (model.last_session_stats)."""
         from .logits_processors import refuse_unsupported
         gc = self._resolve_generation_config(generation_config, kwargs)
         refuse_unsupported(gc, kwargs)                            # nothing the caller switched on is dropped silently
@@ -752,10 +781,21 @@ class VisualCLAModel:
         # prefix_allowed_tokens_fn: the reference forwards it to HF generate (modeling_visualcla.py:382-391), which turns it into a processor placed
         # among the configured ones (it sees the NEW tokens only, as every processor does when HF is driven by inputs_embeds).  Host-driven step path.
         t = self.config.text_config
+        ids_arg = input_ids
         input_ids = self._prepare_ids(input_ids, pixel_values)
         B = input_ids.shape[0]
         if getattr(gc, "prompt_lookup_num_tokens", None) is not None and B != 1:
             raise ValueError(f"prompt_lookup_num_tokens is implemented for batch size 1 (got batch size {B}), as HF's assisted generation")
+        ids_host = None
+        if session is not None:
+            from .session import Session, session_conflicts
+            if not isinstance(session, Session) or session.model is not self:
+                raise ValueError("session must come from this model's new_session()")
+            bad = session_conflicts(gc, B, self.image_at_head, bool(getattr(self, "_kv_fp8", False)))
+            if bad:
+                raise ValueError("session= (K/V reuse across calls) cannot be combined with " + ", ".join(bad))
+            # the planning rule runs on host lists (one copy back when the caller's ids live on the device)
+            ids_host = [int(x) for x in (ids_arg if ids_arg.device.type == "cpu" else input_ids)[0].tolist()]
         if use_graph is None:
             use_graph = os.environ.get("VCLA_DECODE_GRAPH", "1") != "0"
         # hipGraph capture (decode loop; vision stack and prefill inside the engine) is illegal on the legacy default stream: the
@@ -769,7 +809,10 @@ class VisualCLAModel:
             side.wait_stream(cur_stream)
         with torch.cuda.device(self._device), torch.cuda.stream(side if side is not None else cur_stream):
             toks = self._generate_on_stream(gc, input_ids, pixel_values, attention_mask, logits_processor, stopping_criteria, use_graph,
-                                            device_sampling, prefix_allowed_tokens_fn)
+                                            device_sampling, prefix_allowed_tokens_fn, session, ids_host)
+            if session is not None:
+                from .session import record_ids
+                session.ids = record_ids(ids_host, toks[0].tolist())
         if side is not None:
             cur_stream.wait_stream(side)
         return toks
@@ -919,15 +962,35 @@ class VisualCLAModel:
         return out[:count].view(1, count).clone()
 
     def _generate_on_stream(self, gc, input_ids, pixel_values, attention_mask, logits_processor, stopping_criteria, use_graph, device_sampling,
-                            prefix_fn=None):
+                            prefix_fn=None, session=None, ids_host=None):
         lib = _lib.load()
         t = self.config.text_config
         B = input_ids.shape[0]
         persistent = bool(use_graph)
         Q = self.config.visual_resampler_config["num_query_tokens"] if pixel_values is not None else 0
         img_pos, am = self._check_request(input_ids, attention_mask, Q, for_generate=True)       # one host sync; raises before any kernel runs
-        img = self.embed_images(pixel_values, _persistent=persistent) if pixel_values is not None else None
-        embeds, extra = self._embed(input_ids, img, img_pos, _persistent=persistent)
+        P, vision_skipped = 0, False
+        if session is not None:
+            # what the session's cache already holds of this prompt: rows [0, P) stay, rows [P, T) are computed
+            from .session import image_slot_span, plan_reuse
+            if am is not None:
+                raise ValueError("session= (K/V reuse across calls) cannot be combined with an attention_mask that has zeros")
+            session._ensure()
+            px = None if pixel_values is None else pixel_values.to(device=self._device, dtype=self._dtype).contiguous()
+            key = session._key_for(px)
+            span = image_slot_span(ids_host, self._special_ids()[2]) if px is not None else None
+            P, vision_skipped = plan_reuse(session.ids, session.image_key, ids_host, span, key)
+            session.ids = session.ids[:P]             # whatever happens from here on, the rows [0, P) are what the session holds
+            if key != session.image_key:
+                session.image_key, session.image = key, (None if px is None else px.clone())
+            self.last_session_stats = {"reused": P, "prefilled": len(ids_host) - P, "vision_skipped": vision_skipped}
+        if vision_skipped:
+            embeds, extra = self._embed(input_ids[:, P:], None, None, _persistent=persistent)       # text rows behind the image slot
+        else:
+            img = self.embed_images(pixel_values, _persistent=persistent) if pixel_values is not None else None
+            embeds, extra = self._embed(input_ids, img, img_pos, _persistent=persistent)
+            if P:
+                embeds = embeds[:, P:]
         nrs = int(gc.num_return_sequences or 1)
         if nrs > 1 and int(gc.num_beams or 1) == 1:
             # sampling with several returned sequences: as HF does with inputs_embeds, every prompt's spliced embeddings are repeated num_return_sequences
@@ -936,20 +999,29 @@ class VisualCLAModel:
             embeds = embeds.repeat_interleave(nrs, dim=0).contiguous()
             am = None if am is None else am.repeat_interleave(nrs, dim=0)
             B, persistent, use_graph = B * nrs, False, False
-        T = embeds.shape[1]
-        max_pos = t["max_position_embeddings"]
+        T = P + embeds.shape[1]
+        max_pos = t["max_position_embeddings"] if session is None else session.capacity
         from .logits_processors import new_token_budget
         n_new = min(new_token_budget(gc, T), max_pos - T)         # max_new_tokens, else max_length less the prompt, else 20 (HF's rules for inputs_embeds)
         if n_new <= 0:
-            raise ValueError(f"prompt of {T} tokens leaves no room under max_position_embeddings={max_pos}")
+            raise ValueError(f"prompt of {T} tokens leaves no room under " + (f"max_position_embeddings={max_pos}" if session is None else
+                                                                           f"the session's capacity of {max_pos} tokens (new_session(max_tokens=))"))
         lookup_k = self._lookup_k(gc, T, n_new, max_pos)
         ctx_max = min(max_pos, (T + n_new + lookup_k + 63) // 64 * 64)    # the rows of the last verify pass stay inside the cache
         eos = self._eos_list(gc)
         if int(gc.num_beams or 1) > 1:
             return self._beam_generate(gc, embeds, am, T, n_new, ctx_max, eos, logits_processor, stopping_criteria, prefix_fn)
-        cache = self._new_cache(B, ctx_max, _persistent=persistent)
-        key_mask = self._key_mask(am, B, T, ctx_max)
-        logits = self._prefill(embeds, cache, key_mask, all_logits=False, _persistent=persistent)
+        if session is not None:
+            # the session's own rows, prefilled and decoded in place.  Nothing reused: the prefill of a call without a session
+            ctx_max = session.capacity
+            cache = VclaCache(session.kv, P, ctx_max)
+            key_mask = None
+            logits = self._extend(embeds, cache, _persistent=persistent) if P else self._prefill(embeds, cache, None, all_logits=False, _persistent=persistent)
+            session.ids = list(ids_host)
+        else:
+            cache = self._new_cache(B, ctx_max, _persistent=persistent)
+            key_mask = self._key_mask(am, B, T, ctx_max)
+            logits = self._prefill(embeds, cache, key_mask, all_logits=False, _persistent=persistent)
 
         pad_id = gc.pad_token_id if gc.pad_token_id is not None else (eos[0] if eos else 0)
         procs = self._processors(gc, logits_processor, T, n_new, prefix_fn)
@@ -1003,7 +1075,8 @@ class VisualCLAModel:
                     done_at = step
                     break
             toks = out[:min(step, done_at)].t().contiguous()
-            self._check_decode_status(B, ws)
+            if step > 1:                                      # (no step ran: the workspace holds no engine state to read)
+                self._check_decode_status(B, ws)
             if eos:
                 is_eos = torch.isin(toks, torch.tensor(eos, device=self._device))
                 after = (is_eos.cumsum(dim=1) - is_eos.int()) > 0
@@ -1025,6 +1098,7 @@ class VisualCLAModel:
         if dev_select and not plain_greedy:
             self._uniforms = torch.rand(n_new, B, device=self._device) if gc.do_sample else None
             samp = _lib.sample_args(uniforms=self._uniforms, history=hist, **samp_kw)
+        stepped = False
         for step in range(n_new):
             scores = logits
             if dev_select:
@@ -1057,7 +1131,9 @@ class VisualCLAModel:
                                                       cache.kv.data_ptr(), ctx_max, _lib.ptr(key_mask),
                                                       step_logits.data_ptr(), None, ws.data_ptr(), ws.numel(), stream))
             logits = step_logits
-        self._check_decode_status(B, ws)
+            stepped = True
+        if stepped:                                           # (no step ran: the workspace holds no engine state to read)
+            self._check_decode_status(B, ws)
         return generated.contiguous()
 
     # ------------------------------------------------------------------ in-flight batching
