@@ -579,6 +579,51 @@ size_t vcla_llama_extend_workspace_bytes(const vcla_ctx* ctx, int T, int ctx_max
 int vcla_llama_extend(vcla_ctx* ctx, const void* inputs_embeds, int T, int pos0, void* kv_cache, int ctx_max, float* logits, void* ws,
                       size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------- ragged admission (prompt prefixes shared between the requests of a queue)
+   A server calls the reference's generate() (models/visualcla/modeling_visualcla.py:349-391) once per request, and every call runs the
+   vision stack and the prefill over the whole prompt, also over the rows -- system prompt, image slot -- that the request shares with
+   others.  Under causal attention the K / V rows [0, P) of a prompt depend on nothing behind P: they are computed once and copied, and
+   only the rows behind each request's shared prefix are computed, for SEVERAL requests in one pass, each at its own start position in
+   its own slot of generate_many's cache.  Additive entries; the ABI version stays 5. */
+typedef struct vcla_extend_seq {
+    int32_t slot;               /* sequence (slot) of the cache the block belongs to; every slot at most once per table             */
+    int32_t pos;                /* p: rows the slot already holds = position of the block's first row (0: nothing shared)           */
+    int32_t rows;               /* R: new rows, 1 .. VCLA_EXTEND_MAX_ROWS, pos + rows <= ctx_max                                     */
+    int32_t row0;               /* first packed row of the block: the blocks lie back to back, row0 = sum of the rows before it     */
+} vcla_extend_seq;
+
+/* vcla_attn_extend for n_seqs blocks of new rows in ONE launch (plus one merge launch), each block in another sequence of a slots cache
+   (the R-row instance of LlamaAttention.forward hf:llama/modeling_llama.py:217-281 per block): qkv [M, 3 H d] bf16, the blocks packed back
+   to back (M = sum rows); k_cache / v_cache [B_slots][H][ctx_max][d]; seqs: HOST memory.  Per block what vcla_attn_extend does for its one
+   sequence: RoPE of q and k at pos + j, the new K / V rows appended to the block's slot at [pos, pos + rows) bitwise as
+   vcla_rope_kv_append writes them, row j attends over keys [0, pos + j] of ITS slot, keys >= pos taken from qkv.  out: [M, H d] row-major,
+   or (out_frag, M <= 64) fragment-major with ceil(M / 16) row tiles.  Slots not in the table and rows outside the blocks are not touched.
+   d = 128 or 64, bf16, no key mask.  (sequence, q-tile, key split) are flattened into a work list chosen from the TOTAL work (the rule is
+   stated in csrc/attention_extend.hip); the list lives at the head of `scratch`: vcla_attn_extend_rows_scratch_bytes(seqs, ...) bytes of
+   16-byte aligned device memory for that table, at most vcla_attn_extend_rows_scratch_bound(M, n_seqs, ...) for any table of n_seqs
+   blocks and M rows.  lists_ready != 0: `scratch` still holds the lists the calling thread's PREVIOUS call wrote for the SAME table
+   (the layers of one decoder pass): the table is neither re-checked nor re-planned; 0 checks, plans and copies the lists there on `stream`. */
+size_t vcla_attn_extend_rows_scratch_bytes(const vcla_extend_seq* seqs, int n_seqs, int H, int d);
+size_t vcla_attn_extend_rows_scratch_bound(int M, int n_seqs, int H, int d);
+int vcla_attn_extend_rows(const void* qkv, void* k_cache, void* v_cache, const float* cos_tab, const float* sin_tab, void* out,
+                          const vcla_extend_seq* seqs, int n_seqs, int M, int B_slots, int H, int d, int ctx_max, float scale, int dtype,
+                          int out_frag, int lists_ready, void* scratch, size_t scratch_bytes, void* stream);
+
+/* Workspace of vcla_llama_extend_rows for at most M packed rows in at most n_seqs blocks on a cache of capacity ctx_max. */
+size_t vcla_llama_extend_rows_workspace_bytes(const vcla_ctx* ctx, int M, int n_seqs, int ctx_max);
+
+/* The decoder over the new rows of n_seqs requests in one pass (the prefill of models/visualcla/modeling_visualcla.py:349-391 for each of
+   them, minus the rows its slot already holds): inputs_embeds [M, hidden] act dtype, the blocks packed back to back as `seqs` (host
+   memory) says; kv_cache [L][2][B_slots][H][ctx_max][d]; logits [n_seqs, vocab] fp32: the LAST row of each block.  Routes:
+     bf16, head dim 128 / 64, every block <= VCLA_EXTEND_MAX_ROWS rows: vcla_attn_extend_rows between the streaming decode GEMMs
+       (2 <= M <= 64 and fragment-major weight copies) or the GEMMs a prefill of M rows picks -- always the bf16 weights, never the fp8
+       decode copies;
+     otherwise (fp32, head dim 32, a longer block): block by block through the kernels of vcla_llama_prefill(B = 1, pos0 = pos) on the
+       block's slot, then one final norm + lm_head over the n_seqs last rows.
+   Not with the e4m3 K/V cache (VCLA_KV_FP8).  Runs eagerly: the table of an admission never repeats. */
+int vcla_llama_extend_rows(vcla_ctx* ctx, const void* inputs_embeds, const vcla_extend_seq* seqs, int n_seqs, void* kv_cache, int B_slots,
+                           int ctx_max, float* logits, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

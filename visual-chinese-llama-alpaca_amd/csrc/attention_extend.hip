@@ -19,7 +19,12 @@
 //   merge     S = 1: the wave normalises and stores.  S > 1: per-split (o, m, l) go to scratch and attn_extend_merge_kernel combines them
 //             (attention_verify.hip's form, one more grid dimension).
 // bf16, head dim 128 or 64, no key mask (a session refuses masked prompts).
+//
+// Second entry, vcla_attn_extend_rows (at the end of the file): the same tile code (ax_block) for the blocks of SEVERAL sequences of a slots
+// cache in one launch -- the ragged admission pass of generate_many(share_prefix=True).  Only the mapping from workgroups to work differs:
+// a 1-D work list of (sequence, q-tile, key split) built on the host, the splits chosen from the total work (rule stated there).
 #include "vcla_common.h"
+#include <vector>
 
 namespace {
 constexpr int XKV = 64;            // keys per tile
@@ -79,11 +84,16 @@ inline ExtendPlan extend_plan(int R, int H, int p) {
 }
 }  // namespace
 
+// One work item of one head: the query rows [qt_idx * QB, ...) of a block of R new rows at positions p .. p + R - 1 against split `split` of S
+// of the key tiles they may see.  qkv: the block's first row; kb / vb: the head's K / V rows of the block's sequence ([ctx_max][D]); out_row0:
+// the block's first row in `out` (0 for a single sequence, its first packed row in vcla_attn_extend_rows); pw0: the [QB][D + 4] fp32 partials
+// of this work item (S > 1); append: this work item writes the head's R new K / V rows.  Shared by both kernels below, which differ only in
+// how a workgroup finds these values.
 template <int D, int NW>
-__global__ __launch_bounds__(NW * 64) void attn_extend_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ kc, bf16_t* __restrict__ vc,
-                                                              const float* __restrict__ cos_tab, const float* __restrict__ sin_tab,
-                                                              bf16_t* __restrict__ out, float* __restrict__ part, int R, int H, int ctx_max, int p,
-                                                              float scale, int out_mt) {
+__device__ __forceinline__ void ax_block(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ kb, bf16_t* __restrict__ vb,
+                                         const float* __restrict__ cos_tab, const float* __restrict__ sin_tab, bf16_t* __restrict__ out, int out_row0,
+                                         float* __restrict__ pw0, int R, int H, int p, float scale, int out_mt, int split, int S, int qt_idx, int h,
+                                         bool append) {
     constexpr int QB = NW * 32, NT = NW * 64;
     constexpr int HALF = D / 2;
     constexpr int KST = D / 32;         // MFMA k-steps over the head dim (Q K^T)
@@ -94,19 +104,16 @@ __global__ __launch_bounds__(NW * 64) void attn_extend_kernel(const bf16_t* __re
     __shared__ __attribute__((aligned(16))) unsigned char lds_all[2 * XKV * D * 2];      // [K tile | V tile]
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int split = blockIdx.x, S = gridDim.x, qt_idx = blockIdx.y, nqt = gridDim.y, h = blockIdx.z;
     const int HD = H * D;
     const int q0 = qt_idx * QB;                  // first query row of this workgroup
     const int qw = q0 + wave * 32;               // first query row of this wave
     const int Tk = p + R;
-    bf16_t* kb = kc + (int64_t)h * ctx_max * D;
-    bf16_t* vb = vc + (int64_t)h * ctx_max * D;
     const bf16_t* qh = qkv + h * D;              // row r: q at qh + r*3HD, k at + HD, v at + 2HD
     const int ql = lane & 15, g = lane >> 4;
     const bool wave_active = qw < R;             // waves past the end only help staging
 
     // ---- the R new rows enter the cache: one workgroup per head writes them, none reads them back
-    if (split == 0 && qt_idx == 0) {
+    if (append) {
         for (int idx = tid; idx < R * (CH / 2); idx += NT) {
             const int r = idx / (CH / 2), i = (idx % (CH / 2)) * 8;
             const bf16_t* krow = qh + (int64_t)r * 3 * HD + HD;
@@ -302,15 +309,28 @@ __global__ __launch_bounds__(NW * 64) void attn_extend_kernel(const bf16_t* __re
             for (int dt = 0; dt < DT; ++dt) {
                 float v[4] = {o[qt][dt][0] * inv, o[qt][dt][1] * inv, o[qt][dt][2] * inv, o[qt][dt][3] * inv};
                 const int k = h * D + dt * 16 + g * 4;
-                Act<bf16_t>::st4(out_mt > 0 ? out + ax_frag_index(qrow, k, out_mt) : out + (int64_t)qrow * HD + k, v);
+                Act<bf16_t>::st4(out_mt > 0 ? out + ax_frag_index(out_row0 + qrow, k, out_mt) : out + (int64_t)(out_row0 + qrow) * HD + k, v);
             }
         } else {
-            float* pw = part + ((((int64_t)h * nqt + qt_idx) * S + split) * QB + (qrow - q0)) * (D + 4);
+            float* pw = pw0 + (int64_t)(qrow - q0) * (D + 4);
 #pragma unroll
             for (int dt = 0; dt < DT; ++dt) *reinterpret_cast<f32x4_t*>(pw + dt * 16 + g * 4) = o[qt][dt];
             if (g == 0) { pw[D] = m_run[qt]; pw[D + 1] = l; }
         }
     }
+}
+
+// grid (key split, q-tile, head) of ONE sequence
+template <int D, int NW>
+__global__ __launch_bounds__(NW * 64) void attn_extend_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ kc, bf16_t* __restrict__ vc,
+                                                              const float* __restrict__ cos_tab, const float* __restrict__ sin_tab,
+                                                              bf16_t* __restrict__ out, float* __restrict__ part, int R, int H, int ctx_max, int p,
+                                                              float scale, int out_mt) {
+    constexpr int QB = NW * 32;
+    const int split = blockIdx.x, S = gridDim.x, qt_idx = blockIdx.y, nqt = gridDim.y, h = blockIdx.z;
+    ax_block<D, NW>(qkv, kc + (int64_t)h * ctx_max * D, vc + (int64_t)h * ctx_max * D, cos_tab, sin_tab, out, 0,
+                    part + (((int64_t)h * nqt + qt_idx) * S + split) * QB * (D + 4), R, H, p, scale, out_mt, split, S, qt_idx, h,
+                    split == 0 && qt_idx == 0);
 }
 
 // S > 1: out[r, h, :] = sum_s o_s 2^(m_s - m) / sum_s l_s 2^(m_s - m).  A thread owns 4 consecutive d of one row, a workgroup 256 / (D / 4)
@@ -386,4 +406,192 @@ extern "C" int vcla_attn_extend(const void* qkv, void* k_cache, void* v_cache, c
     if (e.nw == 2) XT_CASE(128, 2);
     XT_CASE(128, 4);
 #undef XT_CASE
+}
+
+// ------------------------------------------------------------------ vcla_attn_extend_rows: the blocks of SEVERAL sequences in one launch
+// n_seqs blocks of new rows packed back to back in qkv [M, 3 H d], block i = R_i rows at positions p_i .. of slot b_i of a slots cache
+// [B_slots][H][ctx_max][d].  Per block exactly what attn_extend_kernel does for its one sequence (the same ax_block); what differs is how a
+// workgroup finds its work.  The host flattens (sequence, q-tile, key split) into a 1-D WORK LIST, grid (n_work, H):
+//   q-tiles   one NW for the launch: 2 waves (64-row q-tiles) when every block has R <= 64, else 4 waves (128-row q-tiles).
+//   splits    chosen from the TOTAL work.  A q-tile sees nt key tiles; NT = the sum over all q-tiles; the launch should be about
+//             X_TARGET_WGS workgroups, i.e. budget = max(1, X_TARGET_WGS / H) work items, so a work item should walk
+//             tpw = max(2, ceil(NT / budget)) key tiles, and q-tile t gets S_t = min(ceil(nt_t / tpw), X_MAX_SPLITS, max(1, nt_t / 2)) splits:
+//             64 short blocks get one split each (they fill the device by their number), one long block gets what attn_extend_kernel
+//             gives it.  Work items with S > 1 number at most 2 * budget, which bounds the partials whatever the table.
+//   merge     one entry per q-tile with S > 1 ({first partial, S, first packed row, rows}); attn_extend_rows_merge_kernel, grid
+//             (entries * QB / rows-per-workgroup, H).
+// The two lists live at the head of the caller's scratch, in front of the partials; the host writes them there (one copy per call, or none
+// when the caller says the scratch still holds the lists of the same table: the 32 layers of one decoder pass).
+namespace {
+struct AxWork { int32_t slot, p, R, m0, qt, split, S, part; };      // part: index of the work item's partials (S > 1)
+struct AxMerge { int32_t part0, S, row0, rows; };
+struct RowsPlan {
+    int nw = 2, qb = 64, n_parts = 0;
+    std::vector<AxWork> work;
+    std::vector<AxMerge> merge;
+};
+inline size_t ax_up256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+inline void rows_plan(const vcla_extend_seq* seqs, int n_seqs, int H, RowsPlan& pl) {
+    pl.work.clear(); pl.merge.clear(); pl.n_parts = 0;
+    int max_r = 0;
+    for (int i = 0; i < n_seqs; ++i) max_r = seqs[i].rows > max_r ? seqs[i].rows : max_r;
+    pl.nw = max_r <= 64 ? 2 : 4;
+    pl.qb = pl.nw * 32;
+    auto tiles_of = [&](const vcla_extend_seq& q, int qt) {
+        const int last_q = ((qt + 1) * pl.qb < q.rows ? (qt + 1) * pl.qb : q.rows) - 1;
+        return (q.pos + last_q + 1 + XKV - 1) / XKV;
+    };
+    int64_t total = 0;
+    for (int i = 0; i < n_seqs; ++i)
+        for (int qt = 0; qt * pl.qb < seqs[i].rows; ++qt) total += tiles_of(seqs[i], qt);
+    const int budget = X_TARGET_WGS / H > 1 ? X_TARGET_WGS / H : 1;
+    int tpw = (int)((total + budget - 1) / budget);
+    tpw = tpw < 2 ? 2 : tpw;
+    for (int i = 0; i < n_seqs; ++i)
+        for (int qt = 0; qt * pl.qb < seqs[i].rows; ++qt) {
+            const int nt = tiles_of(seqs[i], qt);
+            int S = (nt + tpw - 1) / tpw;
+            S = S > X_MAX_SPLITS ? X_MAX_SPLITS : S;
+            const int cap = nt / 2 > 1 ? nt / 2 : 1;
+            S = S < cap ? S : cap;
+            if (S > 1) {
+                const int rows = seqs[i].rows - qt * pl.qb < pl.qb ? seqs[i].rows - qt * pl.qb : pl.qb;
+                pl.merge.push_back(AxMerge{pl.n_parts, S, seqs[i].row0 + qt * pl.qb, rows});
+            }
+            for (int sp = 0; sp < S; ++sp)
+                pl.work.push_back(AxWork{seqs[i].slot, seqs[i].pos, seqs[i].rows, seqs[i].row0, qt, sp, S, S > 1 ? pl.n_parts + sp : 0});
+            if (S > 1) pl.n_parts += S;
+        }
+}
+inline size_t rows_lists_bytes(size_t n_work, size_t n_merge) { return ax_up256(n_work * sizeof(AxWork)) + ax_up256(n_merge * sizeof(AxMerge)); }
+thread_local RowsPlan g_rows_plan;       // (thread_local: the lists outlive the call that copies them to the device)
+}  // namespace
+
+template <int D, int NW>
+__global__ __launch_bounds__(NW * 64) void attn_extend_rows_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ kc, bf16_t* __restrict__ vc,
+                                                                   const float* __restrict__ cos_tab, const float* __restrict__ sin_tab,
+                                                                   bf16_t* __restrict__ out, float* __restrict__ part, const AxWork* __restrict__ work,
+                                                                   int H, int ctx_max, float scale, int out_mt) {
+    constexpr int QB = NW * 32;
+    const AxWork w = work[blockIdx.x];           // workgroup-uniform: scalar loads, no vector register held for it
+    const int h = blockIdx.y;
+    const int64_t head = ((int64_t)w.slot * H + h) * ctx_max * D;
+    ax_block<D, NW>(qkv + (int64_t)w.m0 * 3 * H * D, kc + head, vc + head, cos_tab, sin_tab, out, w.m0,
+                    part + ((int64_t)w.part * H + h) * QB * (D + 4), w.R, H, w.p, scale, out_mt, w.split, w.S, w.qt, h, w.split == 0 && w.qt == 0);
+}
+
+// the merge of attn_extend_merge_kernel per list entry: partials [part][H][QB][D + 4]
+template <int D>
+__global__ __launch_bounds__(256) void attn_extend_rows_merge_kernel(const float* __restrict__ part, bf16_t* __restrict__ out,
+                                                                    const AxMerge* __restrict__ merge, int H, int QB, int out_mt) {
+    constexpr int LPR = D / 4, RPB = 256 / LPR;
+    const int per = QB / RPB;
+    const AxMerge e = merge[blockIdx.x / per];
+    const int h = blockIdx.y, r = (blockIdx.x % per) * RPB + threadIdx.x / LPR, dd = (threadIdx.x % LPR) * 4;
+    if (r >= e.rows) return;
+    const float* base = part + (((int64_t)e.part0 * H + h) * QB + r) * (D + 4);
+    const int64_t ss = (int64_t)H * QB * (D + 4);
+    float mf = -INFINITY;
+    for (int s = 0; s < e.S; ++s) mf = fmaxf(mf, base[s * ss + D]);
+    const float mu = mf == -INFINITY ? 0.f : mf;
+    float lf = 0.f;
+    f32x4_t of = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+    for (int s = 0; s < e.S; ++s) {
+        const float* pw = base + s * ss;
+        const float a = exp2f(pw[D] - mu);
+        lf += pw[D + 1] * a;
+        of += *reinterpret_cast<const f32x4_t*>(pw + dd) * a;
+    }
+    const float inv = lf > 0.f ? 1.0f / lf : 0.f;
+    float v[4] = {of[0] * inv, of[1] * inv, of[2] * inv, of[3] * inv};
+    const int row = e.row0 + r, k = h * D + dd;
+    Act<bf16_t>::st4(out_mt > 0 ? out + ax_frag_index(row, k, out_mt) : out + (int64_t)row * H * D + k, v);
+}
+
+extern "C" size_t vcla_attn_extend_rows_scratch_bytes(const vcla_extend_seq* seqs, int n_seqs, int H, int d) {
+    if (!seqs || n_seqs <= 0 || H <= 0 || d <= 0) return 0;
+    RowsPlan pl;
+    rows_plan(seqs, n_seqs, H, pl);
+    return rows_lists_bytes(pl.work.size(), pl.merge.size()) + (size_t)pl.n_parts * H * pl.qb * (d + 4) * sizeof(float);
+}
+
+// the most any table of n_seqs blocks with M rows in all can need (what a workspace is sized by before the tables are known)
+extern "C" size_t vcla_attn_extend_rows_scratch_bound(int M, int n_seqs, int H, int d) {
+    if (M <= 0 || n_seqs <= 0 || H <= 0 || d <= 0) return 0;
+    const size_t budget = X_TARGET_WGS / H > 1 ? X_TARGET_WGS / H : 1;
+    const size_t n_qt = (size_t)n_seqs + M / 64;                       // q-tiles: ceil(R_i / 64) <= R_i / 64 + 1 each
+    const size_t n_work = n_qt + 2 * budget;                           // one item per q-tile with S = 1, at most 2 * budget items with S > 1
+    return rows_lists_bytes(n_work, n_qt) + 2 * budget * H * 128 * (d + 4) * sizeof(float);
+}
+
+template <int D, int NW>
+static int launch_extend_rows(const void* qkv, void* kc, void* vc, const float* cos_tab, const float* sin_tab, void* out, int H, int ctx_max, float scale,
+                              int out_mt, const RowsPlan& pl, const AxWork* work, const AxMerge* merge, float* part, hipStream_t s) {
+    attn_extend_rows_kernel<D, NW><<<dim3((unsigned)pl.work.size(), H), NW * 64, 0, s>>>((const bf16_t*)qkv, (bf16_t*)kc, (bf16_t*)vc, cos_tab, sin_tab,
+                                                                                        (bf16_t*)out, part, work, H, ctx_max, scale, out_mt);
+    VCLA_CHECK_LAUNCH("attn_extend_rows_kernel");
+    if (!pl.merge.empty()) {
+        constexpr int RPB = 256 / (D / 4);
+        attn_extend_rows_merge_kernel<D><<<dim3((unsigned)pl.merge.size() * (NW * 32 / RPB), H), 256, 0, s>>>(part, (bf16_t*)out, merge, H, NW * 32, out_mt);
+        VCLA_CHECK_LAUNCH("attn_extend_rows_merge_kernel");
+    }
+    return VCLA_OK;
+}
+
+extern "C" int vcla_attn_extend_rows(const void* qkv, void* k_cache, void* v_cache, const float* cos_tab, const float* sin_tab, void* out,
+                                     const vcla_extend_seq* seqs, int n_seqs, int M, int B_slots, int H, int d, int ctx_max, float scale, int dtype,
+                                     int out_frag, int lists_ready, void* scratch, size_t scratch_bytes, void* stream) {
+    VCLA_REQUIRE(dtype == VCLA_BF16, VCLA_ERR_BAD_DTYPE, "attn_extend_rows: bad dtype %d (bf16 rows and a bf16 cache only)", dtype);
+    VCLA_REQUIRE(d == 64 || d == 128, VCLA_ERR_BAD_SHAPE, "attn_extend_rows: head dim %d not in {64,128}", d);
+    VCLA_REQUIRE(seqs && n_seqs >= 1 && M >= 1 && B_slots >= 1 && n_seqs <= B_slots && H > 0 && ctx_max > 0, VCLA_ERR_BAD_SHAPE,
+                 "attn_extend_rows: n_seqs=%d M=%d B_slots=%d H=%d ctx_max=%d", n_seqs, M, B_slots, H, ctx_max);
+    VCLA_REQUIRE(qkv && k_cache && v_cache && cos_tab && sin_tab && out, VCLA_ERR_BAD_ARG, "attn_extend_rows: null pointer");
+    VCLA_REQUIRE(vcla_aligned(qkv, 16) && vcla_aligned(k_cache, 16) && vcla_aligned(v_cache, 16) && vcla_aligned(out, 16), VCLA_ERR_BAD_ARG,
+                 "attn_extend_rows: qkv, the caches and out must be 16-byte aligned");
+    VCLA_REQUIRE(!out_frag || (M <= 64 && (H * d) % 32 == 0), VCLA_ERR_BAD_ARG, "attn_extend_rows: out_frag needs M <= 64 (got %d) and H*d %% 32 == 0", M);
+    RowsPlan& pl = g_rows_plan;
+    if (!lists_ready) {
+        // the table: blocks packed back to back, inside their slots, every slot once -- checked before anything is written
+        std::vector<char> seen((size_t)B_slots, 0);
+        int next = 0;
+        for (int i = 0; i < n_seqs; ++i) {
+            const vcla_extend_seq& q = seqs[i];
+            VCLA_REQUIRE(q.rows >= 1 && q.rows <= VCLA_EXTEND_MAX_ROWS && q.pos >= 0 && q.pos + q.rows <= ctx_max && q.row0 == next, VCLA_ERR_BAD_SHAPE,
+                         "attn_extend_rows: block %d: rows=%d (1..%d) pos=%d ctx_max=%d row0=%d (expected %d)", i, q.rows, VCLA_EXTEND_MAX_ROWS, q.pos, ctx_max,
+                         q.row0, next);
+            VCLA_REQUIRE(q.slot >= 0 && q.slot < B_slots && !seen[q.slot], VCLA_ERR_BAD_ARG, "attn_extend_rows: block %d: slot %d outside 0..%d or named twice", i,
+                         q.slot, B_slots - 1);
+            seen[q.slot] = 1;
+            next += q.rows;
+        }
+        VCLA_REQUIRE(next == M, VCLA_ERR_BAD_SHAPE, "attn_extend_rows: the blocks hold %d rows, M=%d", next, M);
+        rows_plan(seqs, n_seqs, H, pl);
+    }
+    // lists_ready: the caller vouches that table, H and scratch are those of this thread's previous call; its plan and its checks stand
+    VCLA_REQUIRE(!pl.work.empty(), VCLA_ERR_BAD_ARG, "attn_extend_rows: lists_ready without a previous call on this thread");
+    const size_t wl = ax_up256(pl.work.size() * sizeof(AxWork)), lists = rows_lists_bytes(pl.work.size(), pl.merge.size());
+    const size_t need = lists + (size_t)pl.n_parts * H * pl.qb * (d + 4) * sizeof(float);
+    VCLA_REQUIRE(scratch && vcla_aligned(scratch, 16) && scratch_bytes >= need, VCLA_ERR_WORKSPACE, "attn_extend_rows: scratch %zu < %zu bytes", scratch_bytes,
+                 need);
+    hipStream_t s = (hipStream_t)stream;
+    const AxWork* work = (const AxWork*)scratch;
+    const AxMerge* merge = (const AxMerge*)((char*)scratch + wl);
+    float* part = (float*)((char*)scratch + lists);
+    if (!lists_ready) {
+        VCLA_CHECK_HIP(hipMemcpyAsync((void*)work, pl.work.data(), pl.work.size() * sizeof(AxWork), hipMemcpyHostToDevice, s));
+        if (!pl.merge.empty())
+            VCLA_CHECK_HIP(hipMemcpyAsync((void*)merge, pl.merge.data(), pl.merge.size() * sizeof(AxMerge), hipMemcpyHostToDevice, s));
+    }
+    const int out_mt = out_frag ? (M + 15) / 16 : 0;
+    void *kc = k_cache, *vc = v_cache;
+#define XR_CASE(DD, NN) return launch_extend_rows<DD, NN>(qkv, kc, vc, cos_tab, sin_tab, out, H, ctx_max, scale, out_mt, pl, work, merge, part, s)
+    if (d == 64) {
+        if (pl.nw == 2) XR_CASE(64, 2);
+        XR_CASE(64, 4);
+    }
+    if (pl.nw == 2) XR_CASE(128, 2);
+    XR_CASE(128, 4);
+#undef XR_CASE
 }

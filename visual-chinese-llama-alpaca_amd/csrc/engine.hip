@@ -58,6 +58,13 @@ __global__ __launch_bounds__(256) void bcast_rows_kernel(const T* __restrict__ s
 
 __global__ void advance_pos_kernel(int32_t* pos) { *pos += 1; }
 
+// dst[i, :] = src[rows[i], :] in 16-byte pieces (row_bytes % 16 == 0): the last row of every block of a ragged pass, workgroup i
+__global__ __launch_bounds__(256) void gather_rows_kernel(const uint4* __restrict__ src, uint4* __restrict__ dst, const int32_t* __restrict__ rows, int n16) {
+    const uint4* s = src + (int64_t)rows[blockIdx.x] * n16;
+    uint4* d = dst + (int64_t)blockIdx.x * n16;
+    for (int i = threadIdx.x; i < n16; i += 256) d[i] = s[i];
+}
+
 // End of a decode-loop step, ONE launch instead of three (record_ids + advance_pos + the next step's embed_splice): workgroup b
 //   ids_out[(*pos_dev - step_base) * B + b] = cur[b];   x[b, :] = embed[cur[b], :]  (the next step's decoder input);
 // the last workgroup to finish advances *pos_dev (every workgroup has read it by then) and re-arms the ticket.
@@ -191,6 +198,12 @@ struct vcla_ctx {
         bool extend = false;           // inside vcla_llama_extend with a block vcla_attn_extend takes: the T rows of llama_layer are one sequence's new rows at pos0
         void* extend_scratch = nullptr;
         size_t extend_scratch_bytes = 0;
+        // inside vcla_llama_extend_rows: the T rows of llama_layer are the packed blocks of rows_n sequences of a slots cache (vcla_attn_extend_rows,
+        // which shares extend_scratch); cache_seqs > 0: the cache holds that many sequences whatever llama_layer's B (also its block-by-block route)
+        const vcla_extend_seq* rows_seqs = nullptr;
+        int rows_n = 0;
+        int cache_seqs = 0;
+        bool rows_lists_ready = false;   // the scratch holds the work list of rows_seqs (written by the first layer of the pass)
     } run;
     // cached graphs of the vision stack and of the prefill (~250 / ~290 launches, host-bound at B = 1; run_macro), two shapes in rotation
     // each (e.g. forward(all_logits) and generate()'s prefill, or two batch sizes); of one decode step and of one verify iteration
@@ -789,7 +802,7 @@ static bool gemv_norm(int dt, int M) { return (dt == VCLA_F32) ? (M <= 8) : (M =
 // layers leave behind.
 static bool stream_layers(const vcla_ctx* ctx, int M, int T) {
     const vcla_model_cfg& c = ctx->c;
-    const bool rows = (ctx->run.decode_step && (T == 1 || ctx->run.verify)) || ctx->run.extend;
+    const bool rows = (ctx->run.decode_step && (T == 1 || ctx->run.verify)) || ctx->run.extend || ctx->run.rows_seqs;
     return vcla_knobs_get().dstream && rows && c.act_dtype == VCLA_BF16 && M >= 2 && M <= 64 &&
            ctx->twins_complete && c.t_hidden % 32 == 0 && c.t_inter % 32 == 0;
 }
@@ -804,7 +817,7 @@ static int llama_layer(vcla_ctx* ctx, hipStream_t s, const LlamaLayer& L, const 
     const int D = c.t_hidden, H = c.t_heads, d = D / H, M = B * T;
     const bool kv8 = c.t_kv_fp8 != 0;                   // e4m3 cache rows (bf16 activations; checked at ctx creation)
     const int dkv = dt | (kv8 ? VCLA_KV_FP8 : 0);
-    const size_t per = (size_t)B * H * ctx_max * d * (kv8 ? 1 : e);  // bytes of one K (or V) slab of one layer
+    const size_t per = (size_t)(ctx->run.cache_seqs > 0 ? ctx->run.cache_seqs : B) * H * ctx_max * d * (kv8 ? 1 : e);  // bytes of one K (or V) slab of one layer
     char* kc = (char*)kv_cache + (size_t)(2 * l) * per;
     char* vc = kc + per;
     // 2 <= M <= 64 decode rows with fragment-major weight copies: the streaming GEMMs (gemm_stream.hip).  Every operand is
@@ -842,6 +855,13 @@ static int llama_layer(vcla_ctx* ctx, hipStream_t s, const LlamaLayer& L, const 
                         a_def ? w.ssq : nullptr, a_def ? ctx->run.ssq_parts : 0));
             RUN(vcla_attn_decode_rows(w.qkv, kc, vc, ctx->rope_cos, ctx->rope_sin, w.ao, B, H, d, ctx_max, row_pos, key_mask, ctx_max, scale_, dt,
                                       /*out_frag=*/1, s));
+        } else if (ctx->run.rows_seqs) {
+            // ragged admission: the T packed rows are the blocks of several slots, each at its own position
+            RUN(gemm_ds(ctx, s, w.h, L.wqkv, L.vqkv, nullptr, 0, w.qkv, 3 * D, nullptr, M, 3 * D, D, VCLA_EPI_NONE, 0,
+                        a_def ? w.ssq : nullptr, a_def ? ctx->run.ssq_parts : 0));
+            RUN(vcla_attn_extend_rows(w.qkv, kc, vc, ctx->rope_cos, ctx->rope_sin, w.ao, ctx->run.rows_seqs, ctx->run.rows_n, T, ctx->run.cache_seqs, H, d,
+                                      ctx_max, scale_, dt, /*out_frag=*/1, ctx->run.rows_lists_ready, ctx->run.extend_scratch, ctx->run.extend_scratch_bytes, s));
+            ctx->run.rows_lists_ready = true;
         } else if (ctx->run.extend) {
             // a session's new block: the T rows of one sequence at pos0 .. over its cached rows [0, pos0)
             RUN(gemm_ds(ctx, s, w.h, L.wqkv, L.vqkv, nullptr, 0, w.qkv, 3 * D, nullptr, M, 3 * D, D, VCLA_EPI_NONE, 0,
@@ -895,6 +915,11 @@ static int llama_layer(vcla_ctx* ctx, hipStream_t s, const LlamaLayer& L, const 
         // verify rows: RoPE + KV append + causal attention over the cache, position from pos_dev
         RUN(vcla_attn_verify(w.qkv, kc, vc, ctx->rope_cos, ctx->rope_sin, w.ao, T, H, d, ctx_max, pos0, pos_dev, key_mask, scale, dkv, 0,
                              ctx->run.verify_scratch, ctx->run.verify_scratch_bytes, s));
+    } else if (ctx->run.rows_seqs) {
+        // ragged admission: the blocks of several slots in one launch
+        RUN(vcla_attn_extend_rows(w.qkv, kc, vc, ctx->rope_cos, ctx->rope_sin, w.ao, ctx->run.rows_seqs, ctx->run.rows_n, T, ctx->run.cache_seqs, H, d,
+                                  ctx_max, scale, dt, 0, ctx->run.rows_lists_ready, ctx->run.extend_scratch, ctx->run.extend_scratch_bytes, s));
+        ctx->run.rows_lists_ready = true;
     } else if (ctx->run.extend) {
         // a session's new block: RoPE + KV append + causal attention over the cache in one launch, keys split over workgroups
         RUN(vcla_attn_extend(w.qkv, kc, vc, ctx->rope_cos, ctx->rope_sin, w.ao, T, H, d, ctx_max, pos0, scale, dt, 0, ctx->run.extend_scratch,
@@ -1078,6 +1103,113 @@ extern "C" int vcla_llama_extend(vcla_ctx* ctx, const void* inputs_embeds, int T
     // the last row only; every route leaves the residual stream row-major in w.x
     RUN(vcla_rmsnorm((char*)w.x + (size_t)(T - 1) * D * e, D, ctx->norm_g, w.hl, D, 1, D, c.t_eps, c.act_dtype, s));
     return gemm(ctx, s, w.hl, D, ctx->lm_head, nullptr, nullptr, 0, logits, c.t_vocab, 1, c.t_vocab, D, VCLA_EPI_NONE, 1);
+}
+
+// ------------------------------------------------------------------ ragged admission: the new rows of several requests in one pass
+// inputs_embeds holds the blocks of n_seqs requests back to back (M rows); block i = seqs[i].rows rows at positions seqs[i].pos .. of slot
+// seqs[i].slot of a slots cache [L][2][B_slots][H][ctx_max][d].  Two routes:
+//   kernel   bf16, head dim 128 / 64, every block <= VCLA_EXTEND_MAX_ROWS rows: llama_layer ONCE over the M packed rows in its `rows` mode
+//            -- the GEMMs see M rows (streaming for 2 <= M <= 64, else what a prefill of M rows picks; never the fp8 decode copies),
+//            the attention is vcla_attn_extend_rows, the cache strides come from B_slots.
+//   blocks   otherwise (fp32 -- the parity mode --, head dim 32, a longer block): block by block, llama_layer as vcla_llama_prefill(B = 1,
+//            pos0 = pos) runs it, on the block's slot (the cache pointer moved to the slot, the layer stride still B_slots sequences).
+// Behind either: the last row of every block -> final norm -> hl [n_seqs, D] -> ONE lm_head over n_seqs rows.  Eager: the table of an
+// admission pass never repeats.
+static bool rows_kernel_ok(const vcla_ctx* ctx, const vcla_extend_seq* seqs, int n_seqs) {
+    const vcla_model_cfg& c = ctx->c;
+    const int d = c.t_hidden / c.t_heads;
+    if (c.act_dtype != VCLA_BF16 || c.t_kv_fp8 || !(d == 128 || d == 64)) return false;
+    for (int i = 0; seqs && i < n_seqs; ++i)
+        if (seqs[i].rows > VCLA_EXTEND_MAX_ROWS) return false;
+    return true;
+}
+struct RowsTail { void *hl, *last, *last_idx; };   // [n_seqs, D] normalised last rows, the gathered rows they come from, their packed row numbers
+static size_t carve_extend_rows(const vcla_ctx* ctx, int M, int n_seqs, char* base, LlamaWs* w, RowsTail* tail, void** scratch, size_t* scratch_bytes) {
+    const vcla_model_cfg& c = ctx->c;
+    const size_t lw = carve_llama(ctx, 1, M, base, w);
+    Bump b{base, (lw + 255) & ~(size_t)255, 0};
+    RowsTail t;
+    t.hl = b.take((size_t)n_seqs * c.t_hidden * esz(ctx));
+    t.last = b.take((size_t)n_seqs * c.t_hidden * esz(ctx));
+    t.last_idx = b.take((size_t)n_seqs * sizeof(int32_t));
+    const size_t sb = rows_kernel_ok(ctx, nullptr, 0) ? vcla_attn_extend_rows_scratch_bound(M, n_seqs, c.t_heads, c.t_hidden / c.t_heads) : 0;
+    void* sc = b.take(sb);
+    if (tail) *tail = t;
+    if (scratch) *scratch = sb ? sc : nullptr;
+    if (scratch_bytes) *scratch_bytes = sb;
+    return b.off + 256;
+}
+extern "C" size_t vcla_llama_extend_rows_workspace_bytes(const vcla_ctx* ctx, int M, int n_seqs, int ctx_max) {
+    if (!ctx || M <= 0 || n_seqs <= 0 || n_seqs > M || ctx_max <= 0 || ctx->c.t_layers <= 0) return 0;
+    return carve_extend_rows(ctx, M, n_seqs, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+extern "C" int vcla_llama_extend_rows(vcla_ctx* ctx, const void* inputs_embeds, const vcla_extend_seq* seqs, int n_seqs, void* kv_cache, int B_slots,
+                                      int ctx_max, float* logits, void* ws, size_t ws_bytes, void* stream) {
+    VCLA_KNOBS_SCOPE();
+    VCLA_REQUIRE(ctx && ctx->finalized && ctx->c.t_layers > 0, VCLA_ERR_BAD_ARG, "llama_extend_rows: context not finalized, or vision-only");
+    VCLA_REQUIRE(inputs_embeds && seqs && kv_cache && logits && ws, VCLA_ERR_BAD_ARG, "llama_extend_rows: null pointer");
+    const vcla_model_cfg& c = ctx->c;
+    VCLA_REQUIRE(!c.t_kv_fp8, VCLA_ERR_BAD_ARG, "llama_extend_rows: the e4m3 K/V cache is not supported -- nothing was written");
+    VCLA_REQUIRE(n_seqs >= 1 && B_slots >= 1 && n_seqs <= B_slots && ctx_max > 0 && ctx_max <= c.t_max_pos, VCLA_ERR_BAD_SHAPE,
+                 "llama_extend_rows: n_seqs=%d B_slots=%d ctx_max=%d (max_pos %d)", n_seqs, B_slots, ctx_max, c.t_max_pos);
+    // the whole table before anything is written: packed back to back, inside the slots, every slot once
+    std::vector<char> seen((size_t)B_slots, 0);
+    int M = 0;
+    for (int i = 0; i < n_seqs; ++i) {
+        const vcla_extend_seq& q = seqs[i];
+        VCLA_REQUIRE(q.rows >= 1 && q.pos >= 0 && q.pos + q.rows <= ctx_max && q.row0 == M, VCLA_ERR_BAD_SHAPE,
+                     "llama_extend_rows: block %d: rows=%d pos=%d ctx_max=%d row0=%d (expected %d)", i, q.rows, q.pos, ctx_max, q.row0, M);
+        VCLA_REQUIRE(q.slot >= 0 && q.slot < B_slots && !seen[q.slot], VCLA_ERR_BAD_ARG, "llama_extend_rows: block %d: slot %d outside 0..%d or named twice",
+                     i, q.slot, B_slots - 1);
+        seen[q.slot] = 1;
+        M += q.rows;
+    }
+    VCLA_REQUIRE(ws_bytes >= vcla_llama_extend_rows_workspace_bytes(ctx, M, n_seqs, ctx_max), VCLA_ERR_WORKSPACE,
+                 "llama_extend_rows: workspace %zu < %zu bytes", ws_bytes, vcla_llama_extend_rows_workspace_bytes(ctx, M, n_seqs, ctx_max));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t e = esz(ctx);
+    const int D = c.t_hidden, H = c.t_heads, d = D / H;
+    LlamaWs w;
+    RowsTail tail{};
+    void* scratch = nullptr;
+    size_t scratch_bytes = 0;
+    carve_extend_rows(ctx, M, n_seqs, align256(ws), &w, &tail, &scratch, &scratch_bytes);
+    void* hl = tail.hl;
+    ctx->run.splitk_ws = w.splitk;
+    const RunScope scope(ctx);
+    ctx->run.q8_ws = w.q8; ctx->run.q8s_ws = w.q8s;
+    ctx->run.cache_seqs = B_slots;
+    auto gamma_after = [&](int l) { return l + 1 < c.t_layers ? ctx->llama[l + 1].ln1g : nullptr; };
+    if (rows_kernel_ok(ctx, seqs, n_seqs)) {
+        ctx->run.rows_seqs = seqs;
+        ctx->run.rows_n = n_seqs;
+        ctx->run.rows_lists_ready = false;
+        ctx->run.extend_scratch = scratch;
+        ctx->run.extend_scratch_bytes = scratch_bytes;
+        VCLA_CHECK_HIP(hipMemcpyAsync(w.x, inputs_embeds, (size_t)M * D * e, hipMemcpyDeviceToDevice, s));
+        for (int l = 0; l < c.t_layers; ++l)
+            RUN(llama_layer(ctx, s, ctx->llama[l], w, l, 1, M, 0, nullptr, kv_cache, ctx_max, nullptr, l > 0, gamma_after(l)));
+        // every route leaves the residual stream row-major in w.x: gather the last row of each block, ONE final norm over n_seqs rows -> hl
+        static thread_local std::vector<int32_t> last_rows;      // (outlives the call that copies it to the device)
+        last_rows.resize((size_t)n_seqs);
+        for (int i = 0; i < n_seqs; ++i) last_rows[i] = seqs[i].row0 + seqs[i].rows - 1;
+        VCLA_CHECK_HIP(hipMemcpyAsync(tail.last_idx, last_rows.data(), (size_t)n_seqs * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        VCLA_REQUIRE((D * e) % 16 == 0, VCLA_ERR_BAD_SHAPE, "llama_extend_rows: hidden size %d rows are not whole 16-byte pieces", D);
+        gather_rows_kernel<<<n_seqs, 256, 0, s>>>((const uint4*)w.x, (uint4*)tail.last, (const int32_t*)tail.last_idx, (int)(D * e / 16));
+        VCLA_CHECK_LAUNCH("gather_rows_kernel");
+        RUN(vcla_rmsnorm(tail.last, D, ctx->norm_g, hl, D, n_seqs, D, c.t_eps, c.act_dtype, s));
+    } else {
+        for (int i = 0; i < n_seqs; ++i) {
+            const vcla_extend_seq& q = seqs[i];
+            char* slot_kv = (char*)kv_cache + (size_t)q.slot * H * ctx_max * d * e;
+            VCLA_CHECK_HIP(hipMemcpyAsync(w.x, (const char*)inputs_embeds + (size_t)q.row0 * D * e, (size_t)q.rows * D * e, hipMemcpyDeviceToDevice, s));
+            for (int l = 0; l < c.t_layers; ++l)
+                RUN(llama_layer(ctx, s, ctx->llama[l], w, l, 1, q.rows, q.pos, nullptr, slot_kv, ctx_max, nullptr, l > 0, gamma_after(l)));
+            RUN(vcla_rmsnorm((char*)w.x + (size_t)(q.rows - 1) * D * e, D, ctx->norm_g, (char*)hl + (size_t)i * D * e, D, 1, D, c.t_eps, c.act_dtype, s));
+        }
+    }
+    return gemm(ctx, s, hl, D, ctx->lm_head, nullptr, nullptr, 0, logits, c.t_vocab, n_seqs, c.t_vocab, D, VCLA_EPI_NONE, 1);
 }
 
 // The persistent decode step serves B = 1 in the bf16 mode when its weight stream is registered, no fp8 decode copies are loaded (those

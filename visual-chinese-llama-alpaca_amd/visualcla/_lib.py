@@ -138,6 +138,22 @@ def lookup_args(k, ngram_max, budget, eos_ids, row, history, out, state, filler=
 EXTEND_MAX_ROWS = 256       # VCLA_EXTEND_MAX_ROWS: new rows of a session's turn vcla_attn_extend takes (longer blocks are a prefill)
 EXTEND_QTILE_ROWS = 128     # VCLA_EXTEND_QTILE_ROWS: query rows per workgroup above 64 rows
 
+
+class ExtendSeq(C.Structure):
+    """vcla_extend_seq: one block of a ragged pass"""
+    _fields_ = [("slot", C.c_int32), ("pos", C.c_int32), ("rows", C.c_int32), ("row0", C.c_int32)]
+
+
+def extend_seqs(table):
+    """[(slot, pos, rows), ...] -> (vcla_extend_seq array in host memory with row0 filled in, packed rows M)"""
+    arr = (ExtendSeq * len(table))()
+    m = 0
+    for i, (slot, pos, rows) in enumerate(table):
+        arr[i].slot, arr[i].pos, arr[i].rows, arr[i].row0 = int(slot), int(pos), int(rows), m
+        m += int(rows)
+    return arr, m
+
+
 SLOT_MAX_EOS = 8            # VCLA_SLOT_MAX_EOS
 SLOT_SUMMARY_WORDS = 4      # VCLA_SLOT_SUMMARY_WORDS: slots still active, the launch's arrival counter, two reserved words
 
@@ -217,6 +233,11 @@ SYMBOLS = {
     "vcla_attn_extend": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _i, _vp, _sz, _vp]),
     "vcla_llama_extend_workspace_bytes": (_sz, [_vp, _i, _i]),
     "vcla_llama_extend": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _sz, _vp]),
+    "vcla_attn_extend_rows_scratch_bytes": (_sz, [_vp, _i, _i, _i]),
+    "vcla_attn_extend_rows_scratch_bound": (_sz, [_i, _i, _i, _i]),
+    "vcla_attn_extend_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _i, _i, _vp, _sz, _vp]),
+    "vcla_llama_extend_rows_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
+    "vcla_llama_extend_rows": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _sz, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

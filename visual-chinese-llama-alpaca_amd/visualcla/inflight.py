@@ -49,6 +49,7 @@ class Group:
     slots: List[int] = field(default_factory=list)
     T: int = 0                  # longest prompt of the group = the position its rows decode from
     image: bool = False
+    ragged: bool = False        # share_prefix: no padding, every request at position 0 of its slot and decoding from its own T
 
 
 class InflightScheduler:
@@ -56,10 +57,14 @@ class InflightScheduler:
 
     prompt_lens[i]: positions request i's prompt occupies in the decoder (image positions included); budgets[i]: its max_new_tokens;
     has_image[i].  Budgets are clipped to max_position_embeddings - T as generate() clips; a prompt that leaves no room raises
-    ValueError naming the request.  ctx_max = min(max_position_embeddings, round_up_64(max T + max budget)), once for the queue."""
+    ValueError naming the request.  ctx_max = min(max_position_embeddings, round_up_64(max T + max budget)), once for the queue.
+
+    share_prefix: admission is RAGGED (visualcla/prefix.py) -- the requests admitted at one boundary form ONE group
+    whatever their lengths and images, nobody is padded, and request i decodes from its own T_i.  Who is admitted when, and into which
+    slot, does not change."""
 
     def __init__(self, prompt_lens: Sequence[int], budgets: Sequence[int], has_image: Sequence[bool], max_batch: int,
-                 max_position_embeddings: int, image_at_head: bool = False, steps_per_sync: int = 8):
+                 max_position_embeddings: int, image_at_head: bool = False, steps_per_sync: int = 8, share_prefix: bool = False):
         if max_batch < 1:
             raise ValueError(f"max_batch must be at least 1 (got {max_batch})")
         if steps_per_sync < 1:
@@ -78,6 +83,7 @@ class InflightScheduler:
         self.slots = min(int(max_batch), max(self.n, 1))
         self.steps_per_sync = int(steps_per_sync)
         self.image_at_head = bool(image_at_head)
+        self.share_prefix = bool(share_prefix)
         self.cap = max(self.budget, default=1)                   # rows of the history / uniforms buffers
         self.ctx_max = min(self.max_pos, round_up(max(self.T, default=0) + self.cap, 64))
         self.queue = deque(range(self.n))
@@ -108,17 +114,21 @@ class InflightScheduler:
             if self.slot_req[b] is not None:
                 raise ValueError(f"slot {b} still holds request {self.slot_req[b]}")
             i = self.queue.popleft()
-            g = next((g for g in groups if self._fits(g, i)), None)
+            if self.share_prefix:
+                g = groups[0] if groups else None                # T_i + budget_i <= ctx_max holds for every request by construction
+            else:
+                g = next((g for g in groups if self._fits(g, i)), None)
             if g is None:
-                g = Group(image=self.has_image[i])
+                g = Group(image=self.has_image[i], ragged=self.share_prefix)
                 groups.append(g)
             g.requests.append(i)
             g.slots.append(b)
             g.T = max(g.T, self.T[i])
+            g.image = g.image or self.has_image[i]
             self.slot_req[b] = i
         for g in groups:
             for i in g.requests:
-                self.decode_from[i] = g.T
+                self.decode_from[i] = self.T[i] if g.ragged else g.T
         self.stats["admission_groups"] += len(groups)
         return groups
 
@@ -183,12 +193,13 @@ def static_batch_steps(budgets: Sequence[int], slots: int) -> int:
 
 
 def simulate(budgets: Sequence[int], slots: int, steps_per_sync: int, eos_at: Optional[Dict[int, int]] = None, prompt_lens=None, has_image=None,
-             max_position_embeddings: int = 1 << 20, image_at_head: bool = False):
+             max_position_embeddings: int = 1 << 20, image_at_head: bool = False, share_prefix: bool = False):
     """Drives a scheduler with the host model of the slot step and a stepper that emits token (request, k) = 1000 * request + k, or the
     eos id 0 as request i's eos_at[i]-th token.  Returns (scheduler, log of (boundary, slot, request) admissions)."""
     n = len(budgets)
     eos_at = eos_at or {}
-    sch = InflightScheduler(prompt_lens or [4] * n, budgets, has_image or [False] * n, slots, max_position_embeddings, image_at_head, steps_per_sync)
+    sch = InflightScheduler(prompt_lens or [4] * n, budgets, has_image or [False] * n, slots, max_position_embeddings, image_at_head, steps_per_sync,
+                            share_prefix)
     B = sch.slots
     row_pos, count, bud, cur = [-1] * B, [0] * B, [0] * B, [0] * B
     history = [[0] * B for _ in range(sch.cap)]
@@ -209,7 +220,7 @@ def simulate(budgets: Sequence[int], slots: int, steps_per_sync: int, eos_at: Op
                     ended = first == 0 or sch.budget[i] == 1
                     sch.started(b, first, ended)
                     if not ended:
-                        row_pos[b], count[b], bud[b], cur[b] = g.T, 1, sch.budget[i], first
+                        row_pos[b], count[b], bud[b], cur[b] = sch.decode_from[i], 1, sch.budget[i], first
                         history[0][b] = first
         if sch.finished:
             break

@@ -167,10 +167,11 @@ def chat(model, image: Union[str, "Image.Image", torch.Tensor], text: str, histo
 
 
 @torch.inference_mode()
-def chat_many(model, items, generation_config=None, max_batch=64):
+def chat_many(model, items, generation_config=None, max_batch=64, share_prefix=False):
     """The bulk form of chat(): items = [(image, text) or (image, text, history), ...] -> [(response, history), ...].  Every prompt is built as
     chat() builds it, the queue is answered by model.generate_many (in-flight batching over max_batch slots) and every response is appended
-    to its item's history exactly as chat() appends it."""
+    to its item's history exactly as chat() appends it.  share_prefix: generate_many's switch -- the system prompt every item begins with and the
+    image slot of items about one image are computed once."""
     encs, histories = [], []
     for item in items:
         if len(item) not in (2, 3):
@@ -182,7 +183,7 @@ def chat_many(model, items, generation_config=None, max_batch=64):
     if not encs:
         return []
     outs = model.generate_many([dict(input_ids=e.input_ids[0], attention_mask=e.attention_mask[0], pixel_values=e.pixel_values) for e in encs],
-                               max_batch=max_batch, generation_config=gc)
+                               max_batch=max_batch, generation_config=gc, share_prefix=share_prefix)
     results = []
     for toks, history in zip(outs, histories):
         response = model.tokenizer.decode(toks, skip_special_tokens=True)

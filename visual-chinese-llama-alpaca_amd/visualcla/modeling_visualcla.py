@@ -85,6 +85,9 @@ class VisualCLAModel:
         self.generation_config = None
         self._ctx = None
         self._ws: Dict[str, torch.Tensor] = {}
+        # None, or a list: every admission of generate_many then appends (request indices, a copy of their first-token logits [n, V]) -- the
+        # one place these logits exist on the host side; the parity tests of the admission paths read them
+        self._inflight_logits_tap: Optional[list] = None
         with torch.cuda.device(self._device):
             self._packed = packed if packed is not None else random_packed(config, self._device, self._dtype, seed)
             self._build_ctx()
@@ -626,6 +629,25 @@ class VisualCLAModel:
         cache.length = pos0 + Tn
         return logits
 
+    def _extend_rows(self, embeds: torch.Tensor, table, kv: torch.Tensor, ws_for=None):
+        """the decoder over the new rows of several requests in one pass (vcla_llama_extend_rows): embeds [M, D], the
+        blocks of `table` = [(slot, pos, rows), ...] packed back to back; kv [L, 2, B_slots, H, ctx_max, d], block i is appended to its slot
+        at [pos, pos + rows) -> the last-row logits of every block, [len(table), V].  ws_for = (rows, blocks): size the workspace for passes up
+        to that size (one allocation for a whole queue)."""
+        lib = _lib.load()
+        seqs, M = _lib.extend_seqs(table)
+        if embeds.dim() != 2 or embeds.shape[0] != M:
+            raise ValueError(f"_extend_rows: {tuple(embeds.shape)} embeddings for blocks of {M} rows")
+        n, B_slots, ctx_max = len(table), kv.shape[2], kv.shape[4]
+        logits = torch.empty(n, self.config.text_config["vocab_size"], dtype=torch.float32, device=self._device)
+        cap_m, cap_n = ws_for if ws_for is not None else (M, n)
+        ws = self._buf("extend_rows", lib.vcla_llama_extend_rows_workspace_bytes(self._ctx, max(M, cap_m), max(n, cap_n), ctx_max))
+        embeds = embeds.contiguous()
+        with torch.cuda.device(self._device):
+            _lib.check(lib.vcla_llama_extend_rows(self._ctx, embeds.data_ptr(), seqs, n, kv.data_ptr(), B_slots, ctx_max, logits.data_ptr(),
+                                                  ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
+        return logits
+
     def new_session(self, max_tokens: Optional[int] = None):
         """-> visualcla.session.Session: the K/V rows of one conversation, kept between generate(session=) / chat(session=) calls.  Its
         buffer holds `max_tokens` positions (default max_position_embeddings: 1 GiB at the 7B shape in bf16, `session.nbytes`)."""
@@ -1138,9 +1160,11 @@ class VisualCLAModel:
 
     # ------------------------------------------------------------------ in-flight batching
     @staticmethod
-    def _refuse_inflight_conflicts(gc, vocab_size: int = 0, kv_fp8: bool = False, max_budget: int = 0, leftover_kwargs: Optional[dict] = None) -> None:
+    def _refuse_inflight_conflicts(gc, vocab_size: int = 0, kv_fp8: bool = False, max_budget: int = 0, leftover_kwargs: Optional[dict] = None,
+                                   share_prefix: bool = False, image_at_head: bool = False, masked_requests=()) -> None:
         """generate_many decodes on the device-resident slots loop (argmax or the device sampler, one floor for the whole queue): every setting
-        that needs more is refused by name, all of them in one message.  Needs no device."""
+        that needs more is refused by name, all of them in one message.  Needs no device.  share_prefix=True places every prompt un-padded
+        at position 0 of its slot: it also refuses image_at_head=True and the requests (`masked_requests`, by index) whose attention_mask has a zero."""
         from types import SimpleNamespace
         from .logits_processors import _HOST_ONLY_FIELDS, min_token_floor, needs_host_processors, refuse_unsupported
         refuse_unsupported(gc, leftover_kwargs)
@@ -1172,6 +1196,10 @@ class VisualCLAModel:
             bad.append(f"max_new_tokens={max_budget} with logits processors or sampling (the device sampler sees {_lib.SAMPLE_MAX_HIST} tokens)")
         if kv_fp8:
             bad.append("the e4m3 K/V cache (enable_fp8_decode(kv_cache=True))")
+        if share_prefix and image_at_head:
+            bad.append("share_prefix=True with image_at_head=True")
+        if share_prefix and len(masked_requests):
+            bad.append("share_prefix=True with an attention_mask that masks positions (request " + ", ".join(str(i) for i in masked_requests) + ")")
         if bad:
             raise ValueError("generate_many (in-flight batching) cannot be combined with " + ", ".join(bad))
 
@@ -1202,7 +1230,8 @@ class VisualCLAModel:
         return dict(ids=ids, px=row(r.get("pixel_values"), 3, "pixel_values"), am=am, max_new_tokens=mnt)
 
     @torch.no_grad()
-    def generate_many(self, requests, max_batch: int = 64, generation_config=None, steps_per_sync: int = 8, use_graph: Optional[bool] = None, **kwargs):
+    def generate_many(self, requests, max_batch: int = 64, generation_config=None, steps_per_sync: int = 8, use_graph: Optional[bool] = None,
+                      share_prefix: bool = False, prefix_pool_tokens: Optional[int] = None, **kwargs):
         """In-flight batching over a queue: -> List[LongTensor [n_i]] in request order, the NEW tokens of every request, its eos included
         and nothing behind it.  requests: dicts with `input_ids` ([T] or [1, T]), optional `pixel_values`, `attention_mask`, `max_new_tokens`
         (default: the config's budget by generate()'s rules for that prompt).  One generation config for the whole queue.
@@ -1213,7 +1242,14 @@ class VisualCLAModel:
         torch.rand(budget_i) taken from the device generator in request order when the request is admitted.
 
         Greedy, and every config the device sampler covers (repetition penalty, no-repeat-ngram, min_new_tokens, temperature, top-k <= 256,
-        top-p); everything else is refused by name.  model.last_inflight_stats describes the call."""
+        top-p); everything else is refused by name.  model.last_inflight_stats describes the call.
+
+        share_prefix=True: the leading K/V rows that requests of the queue have in common -- a system prompt, the image slot of several
+        questions about one image (compared by value) -- are computed once, kept in a pool of at most `prefix_pool_tokens` rows for the
+        duration of the call and copied into the slots of the requests that share them; only the rows behind are computed, and the vision
+        stack runs once per distinct shared image (visualcla/prefix.py).  Every request sits un-padded at position 0
+        of its slot.  Same results (fp32: the same ids; bf16: within rounding, copied and computed rows come from differently tiled
+        passes).  Refuses image_at_head=True and masked prompts."""
         from .inflight import InflightScheduler
         from .logits_processors import new_token_budget
         gc = self._resolve_generation_config(generation_config, kwargs)
@@ -1222,11 +1258,18 @@ class VisualCLAModel:
         Q = self.config.visual_resampler_config["num_query_tokens"]
         lens = [int(r["ids"].numel()) + (Q if (self.image_at_head and r["px"] is not None) else 0) for r in reqs]
         budgets = [int(r["max_new_tokens"]) if r["max_new_tokens"] is not None else new_token_budget(gc, T) for r, T in zip(reqs, lens)]
+        masked = []
+        if share_prefix:
+            with_mask = [i for i, r in enumerate(reqs) if r["am"] is not None]
+            if with_mask:                                         # one copy back for the whole queue; an all-ones mask is no mask
+                lows = torch.stack([reqs[i]["am"].min() for i in with_mask]).tolist()
+                masked = [i for i, lo in zip(with_mask, lows) if not lo]
         self._refuse_inflight_conflicts(gc, t["vocab_size"], bool(getattr(self, "_kv_fp8", False)),
-                                        max((min(b, t["max_position_embeddings"]) for b in budgets), default=0), kwargs)
+                                        max((min(b, t["max_position_embeddings"]) for b in budgets), default=0), kwargs,
+                                        share_prefix=bool(share_prefix), image_at_head=bool(self.image_at_head), masked_requests=masked)
         # raises for a prompt that leaves no room, by index, before any kernel runs
         sched = InflightScheduler(lens, budgets, [r["px"] is not None for r in reqs], max_batch, t["max_position_embeddings"], self.image_at_head,
-                                  steps_per_sync)
+                                  steps_per_sync, share_prefix=bool(share_prefix))
         if use_graph is None:
             use_graph = os.environ.get("VCLA_DECODE_GRAPH", "1") != "0"
         if sched.slots == 1:
@@ -1242,7 +1285,11 @@ class VisualCLAModel:
             sched.stats["slot_steps_active"] = sched.stats["slot_steps_total"] = sched.stats["steps"]
             sched.stats["admission_groups"] = len(reqs)
             self.last_inflight_stats = dict(sched.stats)
+            if share_prefix:                                      # one slot: nothing is alive to share with
+                self.last_inflight_stats.update(rows_reused=0, rows_computed=sum(lens), vision_runs=sum(r["px"] is not None for r in reqs), pool_entries=0,
+                                                pool_bytes=0)
             return out
+        plan = self._prefix_plan(reqs, sched.slots, prefix_pool_tokens) if share_prefix else None
         cur_stream = torch.cuda.current_stream(self._device)
         side = None
         if use_graph and cur_stream.cuda_stream == 0:          # graph capture is illegal on the legacy default stream (as generate())
@@ -1251,12 +1298,43 @@ class VisualCLAModel:
             side = self._side_stream
             side.wait_stream(cur_stream)
         with torch.cuda.device(self._device), torch.cuda.stream(side if side is not None else cur_stream):
-            out = self._inflight_on_stream(gc, reqs, sched, bool(use_graph))
+            out = self._inflight_on_stream(gc, reqs, sched, bool(use_graph), plan)
         if side is not None:
             cur_stream.wait_stream(side)
         return out
 
-    def _inflight_on_stream(self, gc, reqs, sched, use_graph: bool):
+    def _prefix_plan(self, reqs, slots: int, pool_rows: Optional[int]):
+        """the prefix plan of a queue (visualcla/prefix.py) from its ids and images.  Images are compared BY VALUE, as the vision stack sees
+        them (model dtype), inside this pass: one fingerprint per image (a launch over the stacked images, one copy back) buckets them, one
+        row-wise comparison of every image with the first of its bucket confirms (a second copy back); the same tensor object needs neither."""
+        from . import prefix
+        if pool_rows is not None and int(pool_rows) < 0:
+            raise ValueError(f"prefix_pool_tokens must be >= 0 (got {pool_rows})")
+        keys: List[Optional[int]] = [None] * len(reqs)
+        with_px = [i for i, r in enumerate(reqs) if r["px"] is not None]
+        by_obj: Dict[int, int] = {}
+        firsts = []                                               # the first request of every distinct tensor object
+        for i in with_px:
+            if by_obj.setdefault(id(reqs[i]["px"]), i) == i:
+                firsts.append(i)
+        by_shape: Dict[tuple, List[int]] = {}
+        for i in firsts:
+            by_shape.setdefault(tuple(reqs[i]["px"].shape), []).append(i)
+        for members in by_shape.values():
+            flat = torch.stack([reqs[i]["px"].to(self._dtype) for i in members]).flatten(1)
+            w = torch.linspace(1.0, 2.0, flat.shape[1], device=flat.device, dtype=torch.float32)
+            prints = torch.stack([flat.float().sum(1), (flat.float() * w).sum(1)], dim=1).tolist()
+            rep_of: Dict[tuple, int] = {}
+            cand = [rep_of.setdefault(tuple(fp), k) for k, fp in enumerate(prints)]
+            same = (flat == flat[torch.tensor(cand, device=flat.device)]).all(dim=1).tolist()
+            for k, i in enumerate(members):
+                keys[i] = members[cand[k]] if same[k] else i      # (a fingerprint collision of different images: a key of its own)
+        for i in with_px:
+            keys[i] = keys[by_obj[id(reqs[i]["px"])]]
+        prompts = [r["ids"].tolist() for r in reqs] if len({int(r["ids"].numel()) for r in reqs}) != 1 else torch.stack([r["ids"] for r in reqs]).tolist()
+        return prefix.plan(prompts, keys, self._special_ids()[2] if with_px else None, slots, pool_rows)
+
+    def _inflight_on_stream(self, gc, reqs, sched, use_graph: bool, plan=None):
         import time
         from .logits_processors import min_token_floor
         lib = _lib.load()
@@ -1288,6 +1366,11 @@ class VisualCLAModel:
         samp = _lib.sample_args(uniforms=uni, history=hist, **samp_kw) if samp_kw is not None else None
         count_h = [0] * B
         t_adm = t_steps = 0.0
+        share = None
+        if plan is not None:                                    # the prefix pool of this call: [rows, L, 2, H, d], 2 L H d elements per row
+            n_rows = min(plan.pool_rows, plan.peak_pool_rows)
+            pool = torch.empty(n_rows, t["num_hidden_layers"], 2, H, d, dtype=self._dtype, device=dev)
+            share = dict(plan=plan, pool=pool, free=list(range(n_rows - 1, -1, -1)), rows={}, reused=0, computed=0, vision=0, passes=0, calls=0)
         while not sched.finished:
             t0 = time.perf_counter()
             while True:                                         # a request whose first token ends it frees its slot within the boundary
@@ -1298,7 +1381,10 @@ class VisualCLAModel:
                     for i, b in sorted((i, b) for g in groups for i, b in zip(g.requests, g.slots)):
                         uni[:sched.budget[i], b] = torch.rand(sched.budget[i], device=dev)
                 for g in groups:
-                    self._inflight_admit(g, reqs, sched, eos, samp_kw, uni, kv, km, st, hist, cur, count_h)
+                    if g.ragged:
+                        self._inflight_admit_ragged(g, reqs, sched, eos, samp_kw, uni, kv, km, st, hist, cur, count_h, share)
+                    else:
+                        self._inflight_admit(g, reqs, sched, eos, samp_kw, uni, kv, km, st, hist, cur, count_h)
             t1 = time.perf_counter()
             t_adm += t1 - t0
             if sched.finished:
@@ -1316,6 +1402,11 @@ class VisualCLAModel:
             t_steps += time.perf_counter() - t1
         # beside the counters: host seconds spent in admission / in steps, and the position every request's slot decoded from (its group's longest prompt)
         self.last_inflight_stats = dict(sched.stats, admission_s=t_adm, steps_s=t_steps, ctx_max=ctx_max, decode_from=[sched.decode_from[i] for i in range(sched.n)])
+        if share is not None:
+            self.last_inflight_stats.update(rows_reused=share["reused"], rows_computed=share["computed"], vision_runs=share["vision"],
+                                            pool_entries=len(plan.entries), pool_bytes=share["pool"].numel() * share["pool"].element_size(),
+                                            pool_rows=int(share["pool"].shape[0]), admission_passes=share["passes"], rows_calls=share["calls"],
+                                            workspace_bytes=int(self._ws["extend_rows"].numel()) if "extend_rows" in self._ws else 0)
         return [torch.tensor(toks, dtype=torch.int64, device=dev) for toks in sched.ordered_results()]
 
     def _inflight_admit(self, g, reqs, sched, eos, samp_kw, uni, kv, km, st, hist, cur, count_h) -> None:
@@ -1343,6 +1434,8 @@ class VisualCLAModel:
             raise ValueError(f"generate_many: group of requests {g.requests} embeds to {Tg} positions, the scheduler planned {g.T}")
         own = self._new_cache(G, Tg)
         logits = self._prefill(embeds, own, self._key_mask(am2, G, Tg, Tg), all_logits=False)
+        if self._inflight_logits_tap is not None:
+            self._inflight_logits_tap.append((list(g.requests), logits.detach().clone()))
         sl = torch.tensor(g.slots, device=dev)
         kv[:, :, sl, :, :Tg, :] = own.kv
         km[sl] = 1
@@ -1370,4 +1463,110 @@ class VisualCLAModel:
             cur[lb] = fi
             hist[0, lb] = fi
             for b, _, _ in live:
+                count_h[b] = 1
+
+    RAGGED_MAX_ROWS = 8192      # packed rows of one vcla_llama_extend_rows call (its workspace is sized for them); longer passes are cut
+
+    def _inflight_admit_ragged(self, g, reqs, sched, eos, samp_kw, uni, kv, km, st, hist, cur, count_h, share) -> None:
+        """share_prefix=True: the requests admitted at one boundary, every one at position 0 of its slot.  In the passes of prefix.passes: copy
+        the rows [0, P_i) each request reuses from the pool into its slot (one indexed copy per pass), run the vision stack over the images
+        that are needed, then ONE vcla_llama_extend_rows over the rows [P_i, T_i) of all of them, written straight into the slots; the
+        creators of the pass then leave their leading rows in the pool (one indexed copy)."""
+        from . import prefix
+        dev = self._device
+        B = sched.slots
+        plan, pool = share["plan"], share["pool"]
+        slot_of = dict(zip(g.requests, g.slots))
+        Q = self.config.visual_resampler_config["num_query_tokens"]
+        first_of: Dict[int, int] = {}
+
+        def index(pairs):                                       # [(slot, first row, pool rows)] -> (pool idx, slot idx, row idx) on the device
+            pi = torch.tensor([x for _, _, rows in pairs for x in rows], device=dev)
+            si = torch.tensor([b for b, _, rows in pairs for _ in rows], device=dev)
+            ri = torch.tensor([r0 + k for _, r0, rows in pairs for k in range(len(rows))], device=dev)
+            return pi, si, ri
+        for members in prefix.passes(plan, g.requests):
+            share["passes"] += 1
+            reads = [(slot_of[i], 0, share["rows"][plan.source[i]][:plan.P[i]]) for i in members if plan.P[i] > 0]
+            if reads:
+                pi, si, ri = index(reads)
+                kv[:, :, si, :, ri] = pool[pi]
+            # ---- embeddings of whole prompts, by classes of equal (length, image, vision needed): one check and one splice per class
+            classes: Dict[tuple, List[int]] = {}
+            for i in members:
+                classes.setdefault((int(reqs[i]["ids"].numel()), reqs[i]["px"] is not None, plan.vision_needed[i]), []).append(i)
+            emb_of: Dict[int, torch.Tensor] = {}
+            for (T, has_px, vis), cls in classes.items():
+                ids = torch.stack([reqs[i]["ids"] for i in cls])
+                img_pos, _ = self._check_request(ids, None, Q if has_px else 0, for_generate=True)
+                img = None
+                if vis:
+                    img = self.embed_images(torch.stack([reqs[i]["px"] for i in cls]))
+                    share["vision"] += len(cls)
+                embeds, _ = self._embed(ids, img, img_pos if vis else None)
+                for j, i in enumerate(cls):
+                    emb_of[i] = embeds[j, plan.P[i]:]
+            # ---- the rows behind the shared prefixes, cut into calls of at most RAGGED_MAX_ROWS rows (a block the kernel does not take goes alone)
+            calls, cur_call, m = [], [], 0
+            for i in members:
+                r = plan.T[i] - plan.P[i]
+                alone = r > _lib.EXTEND_MAX_ROWS
+                if cur_call and (alone or m + r > self.RAGGED_MAX_ROWS):
+                    calls.append(cur_call)
+                    cur_call, m = [], 0
+                cur_call.append(i)
+                m += r
+                if alone:
+                    calls.append(cur_call)
+                    cur_call, m = [], 0
+            if cur_call:
+                calls.append(cur_call)
+            for call in calls:
+                table = [(slot_of[i], plan.P[i], plan.T[i] - plan.P[i]) for i in call]
+                logits = self._extend_rows(torch.cat([emb_of[i] for i in call]), table, kv,
+                                           ws_for=(min(self.RAGGED_MAX_ROWS, B * max(plan.T)), B))
+                share["calls"] += 1
+                if self._inflight_logits_tap is not None:
+                    self._inflight_logits_tap.append((list(call), logits.detach().clone()))
+                sl = torch.tensor([slot_of[i] for i in call], device=dev)
+                km[sl] = 1
+                if samp_kw is None:
+                    first = _lib.argmax(logits)
+                else:                                           # the same selector as the steps, at history length 0
+                    u0 = uni[0, sl].view(1, len(call)).contiguous() if uni is not None else None
+                    first = _lib.sample(logits, _lib.sample_args(uniforms=u0, **samp_kw), n_hist=0)
+                for i, tok in zip(call, first.tolist()):          # synchronises
+                    first_of[i] = tok
+            share["reused"] += sum(plan.P[i] for i in members)
+            share["computed"] += sum(plan.T[i] - plan.P[i] for i in members)
+            # ---- the creators of this pass leave their rows in the pool; entries whose last reader this pass held are released
+            made = []
+            for i in members:
+                e = plan.entries.get(i)
+                if e is not None:
+                    share["rows"][i] = [share["free"].pop() for _ in range(e.rows)]
+                    made.append((slot_of[i], 0, share["rows"][i]))
+            if made:
+                pi, si, ri = index(made)
+                pool[pi] = kv[:, :, si, :, ri]
+            for i in members:
+                s_ = plan.source[i]
+                if s_ is not None and plan.entries[s_].last_reader == i:
+                    share["free"].extend(share["rows"].pop(s_))
+        live = []
+        for i, b in zip(g.requests, g.slots):
+            ended = first_of[i] in eos or sched.budget[i] == 1
+            sched.started(b, first_of[i], ended)
+            if not ended:
+                live.append((b, first_of[i], sched.budget[i], plan.T[i]))
+        if live:
+            lb = torch.tensor([x[0] for x in live], device=dev)
+            fi = torch.tensor([x[1] for x in live], dtype=torch.int64, device=dev)
+            st[lb] = torch.tensor([x[3] for x in live], dtype=torch.int32, device=dev)        # row_pos: every slot decodes from its own T
+            st[B + lb] = 1                                      # count
+            st[2 * B + lb] = 1                                  # hist_len
+            st[3 * B + lb] = torch.tensor([x[2] for x in live], dtype=torch.int32, device=dev)
+            cur[lb] = fi
+            hist[0, lb] = fi
+            for b, _, _, _ in live:
                 count_h[b] = 1
