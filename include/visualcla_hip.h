@@ -547,6 +547,50 @@ int vcla_slot_step(const int64_t* ids, const vcla_slot_args* args, const void* e
 int vcla_llama_decode_slots(vcla_ctx* ctx, const vcla_slot_args* slots, int n_steps, void* kv_cache, int ctx_max, const int32_t* key_mask,
                             void* ws, size_t ws_bytes, int use_graph, const vcla_sample_args* sampling, void* stream);
 
+/* ---------------------------------------------------------------- per-request generation configs (one record per slot)
+   A served queue mixes callers: HF builds ONE processor list per generate() call (hf:generation/utils.py _get_logits_processor /
+   _get_stopping_criteria, from that call's GenerationConfig), so requests under different configs are different generate() calls there.
+   Here the parameters of row b's processors, warpers and draw come from a record in DEVICE memory, so one captured slots step serves a
+   queue whose requests each carry their own config (models/visualcla/modeling_utils.py:36-47 is only one of them).  Additive entries;
+   the ABI version stays 5. */
+typedef struct vcla_sample_row {
+    float repetition_penalty;   /* the fields of vcla_sample_args, with the same meaning and the same ranges ...                */
+    int no_repeat_ngram_size;
+    int min_new_tokens;
+    int n_eos;
+    int eos_ids[VCLA_SAMPLE_MAX_EOS];
+    float temperature;
+    int top_k;
+    float top_p_complement;     /* ... except top_p: (float)(1.0 - top_p), the fp32 threshold vcla_sample compares against ...  */
+    int use_top_p;              /* ... and top_p < 1.0                                                                          */
+    int min_tokens_to_keep;
+    int greedy;                 /* != 0: the row ignores its uniform and draws at 0 (with top_k = 1: argmax of the processed scores) */
+    int reserved[2];            /* zero; the record is 64 bytes                                                                 */
+} vcla_sample_row;
+
+/* vcla_sample_rows with one parameter record per row: rows [B] in device memory.  `shared` supplies only uniforms, history and the
+   three taps; its scalar fields are ignored.  Row b equals, bit for bit, vcla_sample on that row alone with rows[b]'s parameters
+   (hf:generation/logits_process.py in the order of hf:generation/utils.py _get_logits_processor, per row); rows with a negative
+   history length are skipped.  The records cannot be range-checked on the host: the caller validates them before the upload (the
+   kernel clamps top_k, n_eos and min_tokens_to_keep into their ranges so that a bad record cannot index out of bounds). */
+int vcla_sample_rows_table(float* logits, int64_t ld, int B, int V, const int32_t* n_hist_rows, const vcla_sample_args* shared,
+                           const vcla_sample_row* rows, int64_t* ids_out, void* stream);
+
+/* vcla_slot_step with one eos list per slot: eos_rows device int32 [B][VCLA_SLOT_MAX_EOS], -1 padded (the per-row form of
+   hf:generation/stopping_criteria.py EosTokenCriteria, which holds ONE list per generate() call).  eos_rows non-NULL: slot b
+   finishes on eos_rows[b][*] instead of args->eos_ids; NULL: vcla_slot_step. */
+int vcla_slot_step_rows(const int64_t* ids, const vcla_slot_args* args, const int32_t* eos_rows, const void* embed_table, void* x, int D,
+                        int V, int dtype, void* stream);
+
+/* vcla_llama_decode_slots with per-slot tables: eos_rows as vcla_slot_step_rows, rows as vcla_sample_rows_table (rows non-NULL needs
+   `sampling` for uniforms / history; its scalar fields are ignored).  Either may be NULL = the uniform behaviour.  The tables live in
+   device memory and are part of the graph key: the host rewrites the records of the slots it fills between two calls and the captured
+   step stays valid, and a capture without tables is never replayed for a call with them (the per-token loop body of
+   hf:generation/utils.py under a config per row). */
+int vcla_llama_decode_slots_rows(vcla_ctx* ctx, const vcla_slot_args* slots, int n_steps, void* kv_cache, int ctx_max,
+                                 const int32_t* key_mask, void* ws, size_t ws_bytes, int use_graph, const vcla_sample_args* sampling,
+                                 const int32_t* eos_rows, const vcla_sample_row* rows, void* stream);
+
 /* ---------------------------------------------------------------- chat sessions (later turns on a kept K/V cache)
    The reference's chat() (models/visualcla/modeling_utils.py:144-178) calls model.generate once per turn with the whole history in the
    prompt, and every call re-runs models/visualcla/modeling_visualcla.py:349-391 over all of it: the vision stack on the same image, then

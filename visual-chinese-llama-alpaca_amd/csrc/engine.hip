@@ -1421,8 +1421,10 @@ extern "C" int vcla_llama_verify_loop(vcla_ctx* ctx, const vcla_lookup_args* arg
 // One step: the decoder over the B slot rows with per-row positions, final norm + lm_head, argmax or the per-row sampler, the slot
 // bookkeeping (slots.hip).  Everything a step reads -- positions, counts, budgets, history, current ids -- lives in device memory, so one
 // captured step serves the whole queue whatever the host admits between two chunks.
-extern "C" int vcla_llama_decode_slots(vcla_ctx* ctx, const vcla_slot_args* slots, int n_steps, void* kv_cache, int ctx_max, const int32_t* key_mask,
-                                       void* ws, size_t ws_bytes, int use_graph, const vcla_sample_args* sampling, void* stream) {
+// eos_rows / rows (vcla_llama_decode_slots_rows): per-slot eos lists and sampler records in device memory; both are part of the graph key.
+extern "C" int vcla_llama_decode_slots_rows(vcla_ctx* ctx, const vcla_slot_args* slots, int n_steps, void* kv_cache, int ctx_max, const int32_t* key_mask,
+                                            void* ws, size_t ws_bytes, int use_graph, const vcla_sample_args* sampling, const int32_t* eos_rows,
+                                            const vcla_sample_row* rows, void* stream) {
     VCLA_KNOBS_SCOPE();
     VCLA_REQUIRE(ctx && ctx->finalized && ctx->c.t_layers > 0, VCLA_ERR_BAD_ARG, "llama_decode_slots: context not finalized, or vision-only");
     RUN(slot_args_check(slots, "llama_decode_slots"));
@@ -1434,6 +1436,7 @@ extern "C" int vcla_llama_decode_slots(vcla_ctx* ctx, const vcla_slot_args* slot
     VCLA_REQUIRE(c.act_dtype != VCLA_BF16 || c.t_hidden % 8 == 0, VCLA_ERR_BAD_SHAPE, "llama_decode_slots: hidden size %d is not a multiple of 8", c.t_hidden);
     VCLA_REQUIRE(!sampling || (slots->hist_len && sampling->history == slots->history), VCLA_ERR_BAD_ARG,
                  "llama_decode_slots: sampling needs slots->hist_len and reads the slots' own history buffer");
+    VCLA_REQUIRE(!rows || sampling, VCLA_ERR_BAD_ARG, "llama_decode_slots_rows: a table of sampler records needs `sampling` (uniforms, history)");
     VCLA_REQUIRE(ws_bytes >= vcla_llama_workspace_bytes(ctx, B, 1), VCLA_ERR_WORKSPACE, "llama_decode_slots: workspace %zu < %zu bytes", ws_bytes,
                  vcla_llama_workspace_bytes(ctx, B, 1));
     if (n_steps == 0) return VCLA_OK;
@@ -1447,14 +1450,20 @@ extern "C" int vcla_llama_decode_slots(vcla_ctx* ctx, const vcla_slot_args* slot
         const RunScope scope(ctx);
         ctx->run.decode_step = true;
         RUN(decoder_rows(ctx, st, w, B, 1, 0, nullptr, kv_cache, ctx_max, key_mask, w.logits, slots->row_pos));
-        if (sampling) RUN(vcla_sample_launch(w.logits, c.t_vocab, B, c.t_vocab, 0, nullptr, sampling, w.ids, st, slots->hist_len));
+        if (sampling) RUN(vcla_sample_launch(w.logits, c.t_vocab, B, c.t_vocab, 0, nullptr, sampling, w.ids, st, slots->hist_len, rows));
         else RUN(vcla_argmax(w.logits, c.t_vocab, w.ids, B, c.t_vocab, st));
-        return vcla_slot_step(w.ids, slots, ctx->embed, w.x, c.t_hidden, c.t_vocab, c.act_dtype, st);
+        return vcla_slot_step_rows(w.ids, slots, eos_rows, ctx->embed, w.x, c.t_hidden, c.t_vocab, c.act_dtype, st);
     };
-    struct { const void *kv_cache, *key_mask, *ws; int ctx_max, has_samp; vcla_slot_args slots; vcla_sample_args samp; } key;
+    struct { const void *kv_cache, *key_mask, *ws, *eos_rows, *rows; int ctx_max, has_samp; vcla_slot_args slots; vcla_sample_args samp; } key;
     memset(&key, 0, sizeof key);
     key.kv_cache = kv_cache; key.key_mask = key_mask; key.ws = ws; key.ctx_max = ctx_max; key.has_samp = sampling != nullptr;
+    key.eos_rows = eos_rows; key.rows = rows;
     memcpy(&key.slots, slots, sizeof(*slots));
     if (sampling) memcpy(&key.samp, sampling, sizeof(*sampling));
     return run_steps(ctx->slots_graph, "slots", key, use_graph, n_steps, s, one_step);
+}
+
+extern "C" int vcla_llama_decode_slots(vcla_ctx* ctx, const vcla_slot_args* slots, int n_steps, void* kv_cache, int ctx_max, const int32_t* key_mask,
+                                       void* ws, size_t ws_bytes, int use_graph, const vcla_sample_args* sampling, void* stream) {
+    return vcla_llama_decode_slots_rows(ctx, slots, n_steps, kv_cache, ctx_max, key_mask, ws, ws_bytes, use_graph, sampling, nullptr, nullptr, stream);
 }

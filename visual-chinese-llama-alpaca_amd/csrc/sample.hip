@@ -49,9 +49,14 @@ struct SampleParams {
 
 static_assert(SAMPLE_THREADS * SAMPLE_PER_THREAD == VCLA_SAMPLE_MAX_VOCAB, "register slice must cover the largest vocabulary");
 
+// TABLE (vcla_sample_rows_table): the scalar parameters of row b come from rows[b] in device memory instead of the by-value block `a`
+// (which then supplies the pointers only).  One workgroup serves one row and the record's address is a function of blockIdx alone, so
+// every field is read ONCE per wave through scalar loads and every parameter-dependent branch around a barrier (penalise, the n-gram
+// test, the bisection bounds, use_top_p) stays workgroup-uniform.  The body below the parameter block is the same for both forms.
+template <bool TABLE>
 __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(float* __restrict__ logits, int64_t ld, int V, int B, int n_hist,
                                                                 const int32_t* __restrict__ n_hist_dev, const int32_t* __restrict__ n_hist_rows,
-                                                                SampleParams a, int64_t* __restrict__ out) {
+                                                                SampleParams a, const vcla_sample_row* __restrict__ rows, int64_t* __restrict__ out) {
     __shared__ int s_hist[SAMPLE_MAX_HIST];
     __shared__ unsigned s_seen[VCLA_SAMPLE_MAX_VOCAB / 32];   // one bit per token id: "already penalised"
     __shared__ int s_cnt[3];
@@ -64,8 +69,20 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(float* __restric
     int h = n_hist_rows ? n_hist_rows[b] : n_hist + (n_hist_dev ? *n_hist_dev : 0);
     if (n_hist_rows && h < 0) return;   // workgroup-uniform, ahead of every barrier
     h = h < 0 ? 0 : (h > SAMPLE_MAX_HIST ? SAMPLE_MAX_HIST : h);
+    const vcla_sample_row* const r = TABLE ? rows + blockIdx.x : nullptr;
+    const float p_rep = TABLE ? r->repetition_penalty : a.repetition_penalty;
+    const int p_ngram = TABLE ? r->no_repeat_ngram_size : a.no_repeat_ngram;
+    const int p_min_new = TABLE ? r->min_new_tokens : a.min_new_tokens;
+    // a record is not range-checked by the launcher (device memory): what indexes LDS or the eos array is clamped here
+    const int p_n_eos = TABLE ? min(max(r->n_eos, 0), VCLA_SAMPLE_MAX_EOS) : a.n_eos;
+    const float p_temp = TABLE ? r->temperature : a.temperature;
+    const int p_top_k = TABLE ? min(max(r->top_k, 1), VCLA_SAMPLE_MAX_TOP_K) : a.top_k;
+    const float p_top_pc = TABLE ? r->top_p_complement : a.top_p_complement;
+    const int p_use_top_p = TABLE ? r->use_top_p : a.use_top_p;
+    const int p_min_keep = TABLE ? max(r->min_tokens_to_keep, 1) : a.min_keep;
+    const bool p_greedy = TABLE ? r->greedy != 0 : false;
     for (int i = tid; i < h; i += SAMPLE_THREADS) s_hist[i] = (int)a.history[(int64_t)i * B + b];
-    const bool penalise = a.repetition_penalty != 1.f && h > 0;
+    const bool penalise = p_rep != 1.f && h > 0;
     if (penalise)
         for (int i = tid; i < VCLA_SAMPLE_MAX_VOCAB / 32; i += SAMPLE_THREADS) s_seen[i] = 0u;
     if (tid < 3) s_cnt[tid] = 0;
@@ -81,13 +98,13 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(float* __restric
             const unsigned bit = 1u << (tok & 31);
             if (!(atomicOr(&s_seen[tok >> 5], bit) & bit)) {
                 const float v = x[tok];
-                x[tok] = v < 0.f ? v * a.repetition_penalty : v / a.repetition_penalty;
+                x[tok] = v < 0.f ? v * p_rep : v / p_rep;
             }
         }
         __syncthreads();
     }
     // ---- NoRepeatNGramLogitsProcessor: ban every token that followed an earlier copy of the last n-1 tokens
-    const int n = a.no_repeat_ngram;
+    const int n = p_ngram;
     if (n > 0 && h + 1 >= n) {
         const int p0 = h + 1 - n;   // the current (n-1)-token prefix is s_hist[p0 .. h)
         for (int i = tid; i + n <= h; i += SAMPLE_THREADS) {
@@ -98,7 +115,10 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(float* __restric
         }
     }
     // ---- MinNewTokensLengthLogitsProcessor
-    if (tid < a.n_eos && h < a.min_new_tokens && a.eos[tid] >= 0 && a.eos[tid] < V) x[a.eos[tid]] = -INFINITY;
+    if (tid < p_n_eos && h < p_min_new) {
+        const int e = TABLE ? r->eos_ids[tid] : a.eos[tid];
+        if (e >= 0 && e < V) x[e] = -INFINITY;
+    }
     __syncthreads();
 
     // ---- this thread's slice of the row goes to registers once (all loads in flight) as order-preserving keys of the
@@ -113,7 +133,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(float* __restric
     // ---- TopKLogitsWarper: bisection on the key for the largest t with count(key >= t) >= k.  A pass is 52 register
     //      compares + a wave reduction + one LDS atomic per wave; it stops as soon as the survivors are few enough to sort
     //      (k <= count <= 2k, at least 64), typically after ~12 passes: 8 fix the exponent, a few the mantissa.
-    const int k = a.top_k < V ? a.top_k : V;
+    const int k = p_top_k < V ? p_top_k : V;
     const int few = 2 * k > 64 ? 2 * k : 64;   // <= SAMPLE_CAP since k <= 256
     unsigned lo = 1u, hi = 0xffffffffu;        // count(key >= 1) = V >= k
     for (int pass = 0; lo < hi; ++pass) {
@@ -145,7 +165,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(float* __restric
             if (lane == 0) base = atomicAdd(&s_ncand, __popcll(m));
             base = __shfl(base, 0, 64);
             const int slot = base + __popcll(m & ((1ull << lane) - 1ull));
-            if (take && slot < SAMPLE_CAP) { s_cv[slot] = funkey(key[j]) / a.temperature; s_ci[slot] = tid + j * SAMPLE_THREADS; }
+            if (take && slot < SAMPLE_CAP) { s_cv[slot] = funkey(key[j]) / p_temp; s_ci[slot] = tid + j * SAMPLE_THREADS; }
         }
     }
     __syncthreads();
@@ -167,7 +187,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(float* __restric
                 if (lane == 0) base = atomicAdd(&s_ncand, __popcll(m));
                 base = __shfl(base, 0, 64);
                 const int slot = base + __popcll(m & ((1ull << lane) - 1ull));
-                if (take) { s_cv[slot] = funkey(key[j]) / a.temperature; s_ci[slot] = tid + j * SAMPLE_THREADS; }
+                if (take) { s_cv[slot] = funkey(key[j]) / p_temp; s_ci[slot] = tid + j * SAMPLE_THREADS; }
             }
         }
         __syncthreads();
@@ -181,7 +201,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(float* __restric
             int before = 0, total = 0;
             for (int w = 0; w < SAMPLE_THREADS / 64; ++w) { const int c = s_wcnt[w]; before += w < (tid >> 6) ? c : 0; total += c; }
             const int slot = filled + before + __popcll(m & ((1ull << lane) - 1ull));
-            if (take && slot < SAMPLE_CAP) { s_cv[slot] = funkey(key[j]) / a.temperature; s_ci[slot] = tid + j * SAMPLE_THREADS; }
+            if (take && slot < SAMPLE_CAP) { s_cv[slot] = funkey(key[j]) / p_temp; s_ci[slot] = tid + j * SAMPLE_THREADS; }
             filled += total;
             __syncthreads();
         }
@@ -222,7 +242,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(float* __restric
 #pragma unroll
         for (int q = E - 1; q >= 0; --q) { e[q] = s_cv[lane * E + q]; part += e[q]; }
         int keep = nc;
-        if (a.use_top_p) {
+        if (p_use_top_p) {
             const float Z = wave_sum(part);
             // ascending cumulative probability = suffix sums over the descending order; the cut keeps every rank whose
             // suffix sum exceeds 1 - top_p (suffix sums fall with rank, so that is a prefix)
@@ -237,10 +257,10 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(float* __restric
 #pragma unroll
             for (int q = E - 1; q >= 0; --q) {
                 c += e[q] / Z;
-                cnt += (lane * E + q < nc) && c > a.top_p_complement;
+                cnt += (lane * E + q < nc) && c > p_top_pc;
             }
             keep = wave_sum_i(cnt);
-            if (keep < a.min_keep) keep = a.min_keep < nc ? a.min_keep : nc;
+            if (keep < p_min_keep) keep = p_min_keep < nc ? p_min_keep : nc;
         }
         if (lane == 0) s_kk = keep;
     }
@@ -262,7 +282,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(float* __restric
 #pragma unroll
         for (int q = 0; q < E; ++q) { e[q] = lane * E + q < keep ? s_cv[lane * E + q] : 0.f; part += e[q]; }
         const float Zk = wave_sum(part);
-        const float u = a.uniforms ? a.uniforms[(int64_t)h * B + b] : 0.f;
+        const float u = a.uniforms && !p_greedy ? a.uniforms[(int64_t)h * B + b] : 0.f;
         const float target = u * Zk;
         float pre = part;   // -> inclusive prefix over lanes
 #pragma unroll
@@ -297,10 +317,24 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(float* __restric
 }
 
 int vcla_sample_launch(float* logits, int64_t ld, int B, int V, int n_hist, const int32_t* n_hist_dev, const vcla_sample_args* a,
-                       int64_t* out, hipStream_t s, const int32_t* n_hist_rows) {
+                       int64_t* out, hipStream_t s, const int32_t* n_hist_rows, const vcla_sample_row* rows) {
     VCLA_REQUIRE(logits && a && out, VCLA_ERR_BAD_ARG, "sample: null pointer");
     VCLA_REQUIRE(B >= 0 && V > 0 && V <= VCLA_SAMPLE_MAX_VOCAB && ld >= V && n_hist >= 0, VCLA_ERR_BAD_SHAPE,
                  "sample: B=%d V=%d (max %d) ld=%lld n_hist=%d", B, V, VCLA_SAMPLE_MAX_VOCAB, (long long)ld, n_hist);
+    if (rows) {   // the table form: the scalar fields of `a` are ignored (the records were range-checked before their upload)
+        VCLA_REQUIRE(n_hist_rows && a->history, VCLA_ERR_BAD_ARG, "sample_rows_table: n_hist_rows or shared->history is NULL");
+        if (B == 0) return VCLA_OK;
+        SampleParams p;
+        memset(&p, 0, sizeof p);
+        p.uniforms = a->uniforms;
+        p.history = a->history;
+        p.kept_ids = a->kept_ids;
+        p.kept_probs = a->kept_probs;
+        p.n_kept = a->n_kept;
+        sample_kernel<true><<<B, SAMPLE_THREADS, 0, s>>>(logits, ld, V, B, 0, nullptr, n_hist_rows, p, rows, out);
+        VCLA_CHECK_LAUNCH("sample_kernel<table>");
+        return VCLA_OK;
+    }
     VCLA_REQUIRE(a->top_k >= 1 && a->top_k <= VCLA_SAMPLE_MAX_TOP_K, VCLA_ERR_BAD_ARG, "sample: top_k=%d outside [1, %d]", a->top_k, VCLA_SAMPLE_MAX_TOP_K);
     VCLA_REQUIRE(a->temperature > 0.f && a->repetition_penalty > 0.f && a->top_p > 0.0 && a->top_p <= 1.0 && a->no_repeat_ngram_size >= 0 &&
                  a->min_tokens_to_keep >= 1 && a->n_eos >= 0 && a->n_eos <= VCLA_SAMPLE_MAX_EOS, VCLA_ERR_BAD_ARG,
@@ -324,7 +358,7 @@ int vcla_sample_launch(float* logits, int64_t ld, int B, int V, int n_hist, cons
     p.kept_ids = a->kept_ids;
     p.kept_probs = a->kept_probs;
     p.n_kept = a->n_kept;
-    sample_kernel<<<B, SAMPLE_THREADS, 0, s>>>(logits, ld, V, B, n_hist, n_hist_dev, n_hist_rows, p, out);
+    sample_kernel<false><<<B, SAMPLE_THREADS, 0, s>>>(logits, ld, V, B, n_hist, n_hist_dev, n_hist_rows, p, nullptr, out);
     VCLA_CHECK_LAUNCH("sample_kernel");
     return VCLA_OK;
 }
@@ -338,4 +372,10 @@ extern "C" int vcla_sample_rows(float* logits, int64_t ld, int B, int V, const i
                                 void* stream) {
     VCLA_REQUIRE(n_hist_rows, VCLA_ERR_BAD_ARG, "sample_rows: n_hist_rows is NULL");
     return vcla_sample_launch(logits, ld, B, V, 0, nullptr, args, ids_out, (hipStream_t)stream, n_hist_rows);
+}
+
+extern "C" int vcla_sample_rows_table(float* logits, int64_t ld, int B, int V, const int32_t* n_hist_rows, const vcla_sample_args* shared,
+                                      const vcla_sample_row* rows, int64_t* ids_out, void* stream) {
+    VCLA_REQUIRE(rows, VCLA_ERR_BAD_ARG, "sample_rows_table: rows is NULL");
+    return vcla_sample_launch(logits, ld, B, V, 0, nullptr, shared, ids_out, (hipStream_t)stream, n_hist_rows, rows);
 }

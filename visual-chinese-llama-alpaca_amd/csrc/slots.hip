@@ -10,8 +10,8 @@
 #include "vcla_common.h"
 
 template <typename T>
-__global__ __launch_bounds__(256) void slot_step_kernel(const int64_t* __restrict__ ids, vcla_slot_args a, const bf16_t* __restrict__ table,
-                                                        T* __restrict__ x, int D, int V) {
+__global__ __launch_bounds__(256) void slot_step_kernel(const int64_t* __restrict__ ids, vcla_slot_args a, const int32_t* __restrict__ eos_rows,
+                                                        const bf16_t* __restrict__ table, T* __restrict__ x, int D, int V) {
     __shared__ int64_t s_id;
     const int b = blockIdx.x;
     if (threadIdx.x == 0) {
@@ -23,7 +23,14 @@ __global__ __launch_bounds__(256) void slot_step_kernel(const int64_t* __restric
             const int c = a.count[b];
             if (c < a.hist_cap) a.history[(int64_t)c * a.B + b] = id;
             bool fin = c + 1 >= a.budget[b];
-            for (int i = 0; i < a.n_eos; ++i) fin = fin || id == (int64_t)a.eos_ids[i];
+            if (eos_rows) {   // vcla_slot_step_rows: the slot's own list, -1 padded
+                for (int i = 0; i < VCLA_SLOT_MAX_EOS; ++i) {
+                    const int e = eos_rows[(int64_t)b * VCLA_SLOT_MAX_EOS + i];
+                    fin = fin || (e >= 0 && id == (int64_t)e);
+                }
+            } else {
+                for (int i = 0; i < a.n_eos; ++i) fin = fin || id == (int64_t)a.eos_ids[i];
+            }
             a.count[b] = c + 1;
             a.row_pos[b] = fin ? -1 : pos + 1;
             if (a.hist_len) a.hist_len[b] = fin ? -1 : c + 1;
@@ -58,7 +65,8 @@ int slot_args_check(const vcla_slot_args* a, const char* who) {
     return VCLA_OK;
 }
 
-extern "C" int vcla_slot_step(const int64_t* ids, const vcla_slot_args* args, const void* embed_table, void* x, int D, int V, int dtype, void* stream) {
+extern "C" int vcla_slot_step_rows(const int64_t* ids, const vcla_slot_args* args, const int32_t* eos_rows, const void* embed_table, void* x, int D,
+                                   int V, int dtype, void* stream) {
     int rc = slot_args_check(args, "slot_step");
     if (rc) return rc;
     VCLA_REQUIRE(ids && embed_table && x && D > 0 && V > 0, VCLA_ERR_BAD_ARG, "slot_step: null pointer, or D=%d V=%d", D, V);
@@ -66,8 +74,12 @@ extern "C" int vcla_slot_step(const int64_t* ids, const vcla_slot_args* args, co
     VCLA_REQUIRE(dtype == VCLA_F32 || (D % 8 == 0 && vcla_aligned(x, 16) && vcla_aligned(embed_table, 16)), VCLA_ERR_BAD_SHAPE,
                  "slot_step: bf16 rows need D %% 8 == 0 (got %d) and 16-byte aligned buffers", D);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == VCLA_BF16) slot_step_kernel<bf16_t><<<args->B, 256, 0, s>>>(ids, *args, (const bf16_t*)embed_table, (bf16_t*)x, D, V);
-    else slot_step_kernel<float><<<args->B, 256, 0, s>>>(ids, *args, (const bf16_t*)embed_table, (float*)x, D, V);
+    if (dtype == VCLA_BF16) slot_step_kernel<bf16_t><<<args->B, 256, 0, s>>>(ids, *args, eos_rows, (const bf16_t*)embed_table, (bf16_t*)x, D, V);
+    else slot_step_kernel<float><<<args->B, 256, 0, s>>>(ids, *args, eos_rows, (const bf16_t*)embed_table, (float*)x, D, V);
     VCLA_CHECK_LAUNCH("slot_step_kernel");
     return VCLA_OK;
+}
+
+extern "C" int vcla_slot_step(const int64_t* ids, const vcla_slot_args* args, const void* embed_table, void* x, int D, int V, int dtype, void* stream) {
+    return vcla_slot_step_rows(ids, args, nullptr, embed_table, x, D, V, dtype, stream);
 }

@@ -42,7 +42,7 @@ int vcla_fail(int code, const char* fmt, ...);
 
 // sample.hip: the launch behind vcla_sample / vcla_sample_rows, shared with the decode loops (n_hist_rows: one history length per sequence)
 int vcla_sample_launch(float* logits, int64_t ld, int B, int V, int n_hist, const int32_t* n_hist_dev, const vcla_sample_args* a,
-                       int64_t* out, hipStream_t s, const int32_t* n_hist_rows = nullptr);
+                       int64_t* out, hipStream_t s, const int32_t* n_hist_rows = nullptr, const vcla_sample_row* rows = nullptr);
 // slots.hip: validation of a slot table, shared with the slots loop
 int slot_args_check(const vcla_slot_args* a, const char* who);
 

@@ -107,6 +107,65 @@ def sample_args(repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0
     return a
 
 
+class SampleRow(C.Structure):
+    """vcla_sample_row: the sampler parameters of ONE batch row, in device memory (vcla_sample_rows_table)"""
+    _fields_ = [
+        ("repetition_penalty", C.c_float), ("no_repeat_ngram_size", C.c_int), ("min_new_tokens", C.c_int),
+        ("n_eos", C.c_int), ("eos_ids", C.c_int * SAMPLE_MAX_EOS),
+        ("temperature", C.c_float), ("top_k", C.c_int), ("top_p_complement", C.c_float), ("use_top_p", C.c_int),
+        ("min_tokens_to_keep", C.c_int), ("greedy", C.c_int), ("reserved", C.c_int * 2),
+    ]
+
+
+_SAMPLE_ROW_KEYS = ("repetition_penalty", "no_repeat_ngram_size", "min_new_tokens", "eos_ids", "temperature", "top_k", "top_p",
+                    "min_tokens_to_keep", "greedy")
+
+
+def sample_row_table(rows):
+    """[sample_args-style kwargs (+ `greedy`), one per batch row] -> a host array of vcla_sample_row.  The records live in device memory,
+    where the launcher cannot range-check them as vcla_sample checks its arguments: the same bounds are checked HERE, before the upload;
+    ValueError names the row."""
+    arr = (SampleRow * max(len(rows), 1))()
+    for b, kw in enumerate(rows):
+        unknown = set(kw) - set(_SAMPLE_ROW_KEYS)
+        if unknown:
+            raise ValueError(f"sample row {b}: unknown fields {sorted(unknown)}")
+        rp, ng, mnt = float(kw.get("repetition_penalty", 1.0)), int(kw.get("no_repeat_ngram_size", 0)), int(kw.get("min_new_tokens", 0))
+        eos = [int(e) for e in kw.get("eos_ids", ())]
+        temp, top_k, top_p = float(kw.get("temperature", 1.0)), int(kw.get("top_k", 1)), float(kw.get("top_p", 1.0))
+        keep = int(kw.get("min_tokens_to_keep", 1))
+        if not 1 <= top_k <= SAMPLE_MAX_TOP_K:
+            raise ValueError(f"sample row {b}: top_k={top_k} outside [1, {SAMPLE_MAX_TOP_K}]")
+        if not (temp > 0.0 and rp > 0.0 and 0.0 < top_p <= 1.0 and ng >= 0 and keep >= 1 and len(eos) <= SAMPLE_MAX_EOS):
+            raise ValueError(f"sample row {b}: temperature={temp:g} repetition_penalty={rp:g} top_p={top_p:g} no_repeat_ngram_size={ng} "
+                             f"min_tokens_to_keep={keep} n_eos={len(eos)} (max {SAMPLE_MAX_EOS})")
+        r = arr[b]
+        r.repetition_penalty, r.no_repeat_ngram_size, r.min_new_tokens, r.n_eos = rp, ng, mnt, len(eos)
+        for i in range(SAMPLE_MAX_EOS):
+            r.eos_ids[i] = eos[i] if i < len(eos) else -1
+        r.temperature, r.top_k, r.min_tokens_to_keep, r.greedy = temp, top_k, keep, int(bool(kw.get("greedy", False)))
+        r.top_p_complement, r.use_top_p = 1.0 - top_p, int(top_p < 1.0)       # the double difference rounded to fp32 by the field, as vcla_sample
+    return arr
+
+
+def sample_row_bytes(arr, n=None) -> torch.Tensor:
+    """the records of sample_row_table as a uint8 host tensor [n, sizeof(vcla_sample_row)], ready for one copy to the device"""
+    n = len(arr) if n is None else int(n)
+    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).view(len(arr), C.sizeof(SampleRow))[:n].clone()
+
+
+def slot_eos_rows(eos_rows) -> torch.Tensor:
+    """per-slot eos lists -> int32 host tensor [B, SLOT_MAX_EOS], -1 padded (the eos_rows of vcla_slot_step_rows)"""
+    out = torch.full((len(eos_rows), SLOT_MAX_EOS), -1, dtype=torch.int32)
+    for b, e in enumerate(eos_rows):
+        e = [int(x) for x in e]
+        if len(e) > SLOT_MAX_EOS:
+            raise ValueError(f"slot {b}: at most {SLOT_MAX_EOS} eos ids (got {len(e)})")
+        if e:
+            out[b, :len(e)] = torch.tensor(e, dtype=torch.int32)
+    return out
+
+
 LOOKUP_MAX_ROWS = 16        # VCLA_LOOKUP_MAX_ROWS: k + 1 verify rows
 LOOKUP_MAX_EOS = 4          # VCLA_LOOKUP_MAX_EOS
 LOOKUP_STATE_WORDS = 8      # VCLA_LOOKUP_STATE_WORDS: n_hist, count, done, iterations, accepted drafts, drafts of the current row
@@ -229,6 +288,9 @@ SYMBOLS = {
     "vcla_sample_rows": (_i, [_vp, _i64, _i, _i, _vp, C.POINTER(SampleArgs), _vp, _vp]),
     "vcla_slot_step": (_i, [_vp, C.POINTER(SlotArgs), _vp, _vp, _i, _i, _i, _vp]),
     "vcla_llama_decode_slots": (_i, [_vp, C.POINTER(SlotArgs), _i, _vp, _i, _vp, _vp, _sz, _i, C.POINTER(SampleArgs), _vp]),
+    "vcla_sample_rows_table": (_i, [_vp, _i64, _i, _i, _vp, C.POINTER(SampleArgs), _vp, _vp, _vp]),
+    "vcla_slot_step_rows": (_i, [_vp, C.POINTER(SlotArgs), _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "vcla_llama_decode_slots_rows": (_i, [_vp, C.POINTER(SlotArgs), _i, _vp, _i, _vp, _vp, _sz, _i, C.POINTER(SampleArgs), _vp, _vp, _vp]),
     "vcla_attn_extend_scratch_bytes": (_sz, [_i, _i, _i, _i]),
     "vcla_attn_extend": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _i, _vp, _sz, _vp]),
     "vcla_llama_extend_workspace_bytes": (_sz, [_vp, _i, _i]),
@@ -430,6 +492,19 @@ def sample(logits, args: SampleArgs, n_hist: int = 0):
     out = torch.empty(logits.shape[0], dtype=torch.int64, device=logits.device)
     check(load().vcla_sample(logits.data_ptr(), logits.stride(0), logits.shape[0], logits.shape[1], int(n_hist), None, C.byref(args),
                              out.data_ptr(), stream_ptr()))
+    return out
+
+
+def sample_rows_table(logits, n_hist_rows, shared: SampleArgs, rows_dev, out=None):
+    """vcla_sample_rows_table: logits [B, V] fp32 (modified in place), n_hist_rows int32 [B] and rows_dev (uint8 [B, sizeof(vcla_sample_row)],
+    from sample_row_bytes) on the device; `shared` carries uniforms / history / taps.  -> ids [B] int64 (skipped rows keep `out`'s value)"""
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+    B = logits.shape[0]
+    assert rows_dev.is_cuda and rows_dev.is_contiguous() and rows_dev.numel() * rows_dev.element_size() >= B * C.sizeof(SampleRow)
+    assert n_hist_rows.dtype == torch.int32 and n_hist_rows.numel() >= B
+    out = torch.empty(B, dtype=torch.int64, device=logits.device) if out is None else out
+    check(load().vcla_sample_rows_table(logits.data_ptr(), logits.stride(0), B, logits.shape[1], n_hist_rows.data_ptr(), C.byref(shared),
+                                        rows_dev.data_ptr(), out.data_ptr(), stream_ptr()))
     return out
 
 

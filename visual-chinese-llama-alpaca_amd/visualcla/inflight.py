@@ -20,10 +20,12 @@ def round_up(x: int, m: int) -> int:
 
 
 def slot_step_model(ids: Sequence[int], row_pos: List[int], count: List[int], budget: Sequence[int], history: List[List[int]],
-                    cur: List[int], eos_ids: Sequence[int], hist_len: Optional[List[int]] = None) -> int:
+                    cur: List[int], eos_ids: Sequence[int], hist_len: Optional[List[int]] = None,
+                    eos_rows: Optional[Sequence[Sequence[int]]] = None) -> int:
     """One step of the slot bookkeeping (csrc/slots.hip), in place: `ids[b]` is the id selected for slot b this step.  An active slot
     (row_pos[b] >= 0) stores it at history[count[b]][b], advances count and position, and finishes (row_pos[b] = -1) on an eos id or
-    when count[b] reaches budget[b]; inactive slots are left alone.  Returns the number of slots still active."""
+    when count[b] reaches budget[b]; inactive slots are left alone.  eos_rows (vcla_slot_step_rows): one eos list per slot, used instead
+    of `eos_ids`.  Returns the number of slots still active."""
     n_active = 0
     for b in range(len(row_pos)):
         if row_pos[b] < 0:
@@ -32,7 +34,7 @@ def slot_step_model(ids: Sequence[int], row_pos: List[int], count: List[int], bu
         c = count[b]
         if c < len(history):
             history[c][b] = t
-        fin = c + 1 >= budget[b] or t in eos_ids
+        fin = c + 1 >= budget[b] or t in (eos_ids if eos_rows is None else eos_rows[b])
         count[b] = c + 1
         row_pos[b] = -1 if fin else row_pos[b] + 1
         if hist_len is not None:

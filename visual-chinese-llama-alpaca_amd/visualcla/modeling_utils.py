@@ -167,11 +167,16 @@ def chat(model, image: Union[str, "Image.Image", torch.Tensor], text: str, histo
 
 
 @torch.inference_mode()
-def chat_many(model, items, generation_config=None, max_batch=64, share_prefix=False):
+def chat_many(model, items, generation_config=None, max_batch=64, share_prefix=False, generation_configs=None, seeds=None):
     """The bulk form of chat(): items = [(image, text) or (image, text, history), ...] -> [(response, history), ...].  Every prompt is built as
     chat() builds it, the queue is answered by model.generate_many (in-flight batching over max_batch slots) and every response is appended
     to its item's history exactly as chat() appends it.  share_prefix: generate_many's switch -- the system prompt every item begins with and the
-    image slot of items about one image are computed once."""
+    image slot of items about one image are computed once.  generation_configs / seeds: optional lists with one entry per item (None: the
+    queue's config / the default generator), forwarded as generate_many's `generation_config` and `seed` request keys -- every item is then
+    answered under its own config, and a seeded item draws the same uniforms whatever else is in the queue."""
+    for name, lst in (("generation_configs", generation_configs), ("seeds", seeds)):
+        if lst is not None and len(lst) != len(items):
+            raise ValueError(f"chat_many: {name} has {len(lst)} entries for {len(items)} items")
     encs, histories = [], []
     for item in items:
         if len(item) not in (2, 3):
@@ -182,8 +187,15 @@ def chat_many(model, items, generation_config=None, max_batch=64, share_prefix=F
         histories.append(history)
     if not encs:
         return []
-    outs = model.generate_many([dict(input_ids=e.input_ids[0], attention_mask=e.attention_mask[0], pixel_values=e.pixel_values) for e in encs],
-                               max_batch=max_batch, generation_config=gc, share_prefix=share_prefix)
+    requests = [dict(input_ids=e.input_ids[0], attention_mask=e.attention_mask[0], pixel_values=e.pixel_values) for e in encs]
+    for i, r in enumerate(requests):
+        if generation_configs is not None and generation_configs[i] is not None:
+            r["generation_config"] = generation_configs[i]
+            if not isinstance(generation_configs[i], dict):       # as _prepare does for the queue's config
+                generation_configs[i].bos_token_id = generation_configs[i].bos_token_id or model.tokenizer.bos_token_id
+        if seeds is not None and seeds[i] is not None:
+            r["seed"] = seeds[i]
+    outs = model.generate_many(requests, max_batch=max_batch, generation_config=gc, share_prefix=share_prefix)
     results = []
     for toks, history in zip(outs, histories):
         response = model.tokenizer.decode(toks, skip_special_tokens=True)

@@ -983,6 +983,16 @@ class VisualCLAModel:
         self.last_lookup_stats = {"k": k, "iterations": int(st[_lib.LOOKUP_ITERS]), "accepted": int(st[_lib.LOOKUP_ACCEPTED]), "tokens": int(count)}
         return out[:count].view(1, count).clone()
 
+    _request_seed: Optional[int] = None     # generate_many's one-slot route: the `seed` of the request generate() is serving (private hook)
+
+    def _draw_uniforms(self, n_new: int, B: int) -> torch.Tensor:
+        """the uniforms of the device sampler, [n_new, B]: the default device generator, or -- under generate_many's `seed` -- the first
+        n_new * B values of a generator of its own seeded with it (B = 1: torch.rand(n_new, generator=g), what a slot of the queue draws)"""
+        if self._request_seed is None:
+            return torch.rand(n_new, B, device=self._device)
+        g = torch.Generator(device=self._device).manual_seed(int(self._request_seed))
+        return torch.rand(n_new * B, device=self._device, generator=g).view(n_new, B)
+
     def _generate_on_stream(self, gc, input_ids, pixel_values, attention_mask, logits_processor, stopping_criteria, use_graph, device_sampling,
                             prefix_fn=None, session=None, ids_host=None):
         lib = _lib.load()
@@ -1072,7 +1082,7 @@ class VisualCLAModel:
             out = self._typed_buf("gen_out", (n_new, B), torch.int64) if persistent else torch.empty(n_new, B, dtype=torch.int64, device=self._device)
             samp = None
             if samp_kw is not None:
-                self._uniforms = torch.rand(n_new, B, device=self._device) if gc.do_sample else None
+                self._uniforms = self._draw_uniforms(n_new, B) if gc.do_sample else None
                 samp = _lib.sample_args(uniforms=self._uniforms, history=out, **samp_kw)
                 with torch.cuda.device(self._device):
                     first = _lib.sample(logits, samp, n_hist=0)
@@ -1118,7 +1128,7 @@ class VisualCLAModel:
         dev_select = not logits_processor and prefix_fn is None and device_sampling is not False and (plain_greedy or samp_kw is not None)
         samp = None
         if dev_select and not plain_greedy:
-            self._uniforms = torch.rand(n_new, B, device=self._device) if gc.do_sample else None
+            self._uniforms = self._draw_uniforms(n_new, B) if gc.do_sample else None
             samp = _lib.sample_args(uniforms=self._uniforms, history=hist, **samp_kw)
         stepped = False
         for step in range(n_new):
@@ -1207,7 +1217,7 @@ class VisualCLAModel:
         """one entry of generate_many's `requests` -> ids [T] int64, pixel_values [C, H, W] or None, attention_mask [T] or None (on the device)"""
         if not isinstance(r, dict) or r.get("input_ids") is None:
             raise ValueError(f"request {i}: a dict with `input_ids` is required")
-        unknown = set(r) - {"input_ids", "pixel_values", "attention_mask", "max_new_tokens"}
+        unknown = set(r) - {"input_ids", "pixel_values", "attention_mask", "max_new_tokens", "generation_config", "seed"}
         if unknown:
             raise ValueError(f"request {i}: unknown keys {sorted(unknown)}")
 
@@ -1227,22 +1237,113 @@ class VisualCLAModel:
         mnt = r.get("max_new_tokens")
         if mnt is not None and (isinstance(mnt, bool) or int(mnt) < 1):
             raise ValueError(f"request {i}: max_new_tokens must be a positive integer (got {mnt!r})")
-        return dict(ids=ids, px=row(r.get("pixel_values"), 3, "pixel_values"), am=am, max_new_tokens=mnt)
+        rc = r.get("generation_config")
+        if rc is not None and not isinstance(rc, dict) and not hasattr(rc, "to_dict"):
+            raise ValueError(f"request {i}: generation_config must be a GenerationConfig or a dict of its fields (got {type(rc).__name__})")
+        seed = r.get("seed")
+        if seed is not None and (isinstance(seed, bool) or not isinstance(seed, int)):
+            raise ValueError(f"request {i}: seed must be an integer (got {seed!r})")
+        return dict(ids=ids, px=row(r.get("pixel_values"), 3, "pixel_values"), am=am, max_new_tokens=mnt, generation_config=rc, seed=seed)
+
+    def _request_configs(self, gc, reqs):
+        """the resolved generation config of every request -> (configs, class of every request, one config per class).  A request without
+        `generation_config` uses the queue's `gc`; a GenerationConfig replaces it and is resolved by _resolve_generation_config as
+        generate()'s own argument is; a dict is laid over the queue's RESOLVED config field by field (nothing the queue set to None on
+        purpose, such as eos_token_id=None, comes back from the model's defaults).  Classes are the distinct resolved configs, in order of
+        first use."""
+        import copy
+        import json
+        gcs, cls, reps, seen = [], [], [], {}
+        for i, r in enumerate(reqs):
+            rc = r["generation_config"]
+            if rc is None:
+                g = gc
+            elif isinstance(rc, dict):
+                left = sorted(k for k in rc if not hasattr(gc, k) or k.startswith("_"))
+                if left:
+                    raise ValueError(f"request {i}: generation_config has fields that are no GenerationConfig fields: {left}")
+                g = copy.deepcopy(gc)
+                for k, v in rc.items():
+                    setattr(g, k, copy.deepcopy(v))
+            else:
+                g = self._resolve_generation_config(rc, {})
+            key = json.dumps(g.to_dict(), sort_keys=True, default=repr)
+            if key not in seen:
+                seen[key] = len(reps)
+                reps.append(g)
+            gcs.append(reps[seen[key]])
+            cls.append(seen[key])
+        return gcs, cls, reps
+
+    @staticmethod
+    def _request_budgets(gc, reqs, gcs, lens) -> List[int]:
+        """max_new_tokens of every request: its `max_new_tokens` key, then the budget its own config states (new_token_budget's rules for
+        a prompt of lens[i] positions), then the queue's"""
+        from transformers import GenerationConfig
+        from .logits_processors import new_token_budget
+
+        def own_budget(rc) -> bool:                               # does the request's config state a budget of its own?
+            get = rc.get if isinstance(rc, dict) else (lambda k: getattr(rc, k, None))
+            return get("max_new_tokens") is not None or (get("max_length") is not None and get("max_length") != GenerationConfig().max_length)
+        return [int(r["max_new_tokens"]) if r["max_new_tokens"] is not None else
+                new_token_budget(g if (r["generation_config"] is not None and own_budget(r["generation_config"])) else gc, T)
+                for r, g, T in zip(reqs, gcs, lens)]
+
+    @staticmethod
+    def _uses_sampler(gc) -> bool:
+        """does a request under this config go through the device sampler in the slots loop (anything but plain greedy)?"""
+        from .logits_processors import min_token_floor
+        rp = gc.repetition_penalty if gc.repetition_penalty is not None else 1.0
+        return bool(gc.do_sample or rp != 1.0 or gc.no_repeat_ngram_size or (VisualCLAModel._eos_list(gc) and min_token_floor(gc, 0) > 0))
+
+    @staticmethod
+    def _refuse_per_request_conflicts(configs, members, budgets, vocab_size: int = 0, kv_fp8: bool = False, share_prefix: bool = False,
+                                      image_at_head: bool = False, masked_requests=()) -> None:
+        """_refuse_inflight_conflicts for a queue whose requests carry their own configs: once per distinct config (`configs[c]` serves the
+        requests `members[c]`, with the sampler limits taken against THEIR budgets), once for what belongs to the queue; ONE ValueError,
+        grouped by reason, naming the requests (`request 3, 7: num_beams=2`).  Needs no device."""
+        head = "generate_many (in-flight batching) cannot be combined with "
+        by_reason: Dict[str, List[int]] = {}
+        for g, idx in zip(configs, members):
+            try:
+                VisualCLAModel._refuse_inflight_conflicts(g, vocab_size, False, max((budgets[i] for i in idx), default=0))
+            except ValueError as e:
+                msg = str(e)
+                by_reason.setdefault(msg[len(head):] if msg.startswith(head) else msg, []).extend(idx)
+        parts = ["request " + ", ".join(str(i) for i in sorted(idx)) + ": " + reason for reason, idx in by_reason.items()]
+
+        class _Unset:                                             # a config that switches nothing on: only the per-queue checks can fire
+            def __getattr__(self, name):
+                return None
+        try:
+            VisualCLAModel._refuse_inflight_conflicts(_Unset(), 0, kv_fp8, 0, None, share_prefix, image_at_head, masked_requests)
+        except ValueError as e:
+            parts.append(str(e)[len(head):])
+        if parts:
+            raise ValueError(head + "; ".join(parts))
 
     @torch.no_grad()
     def generate_many(self, requests, max_batch: int = 64, generation_config=None, steps_per_sync: int = 8, use_graph: Optional[bool] = None,
                       share_prefix: bool = False, prefix_pool_tokens: Optional[int] = None, **kwargs):
         """In-flight batching over a queue: -> List[LongTensor [n_i]] in request order, the NEW tokens of every request, its eos included
         and nothing behind it.  requests: dicts with `input_ids` ([T] or [1, T]), optional `pixel_values`, `attention_mask`, `max_new_tokens`
-        (default: the config's budget by generate()'s rules for that prompt).  One generation config for the whole queue.
+        (default: the config's budget by generate()'s rules for that prompt), `generation_config`, `seed`.
+
+        `generation_config` / the keyword arguments are the queue's config.  A request's own `generation_config` (a GenerationConfig:
+        replaces the queue's; a dict of its fields: laid over the queue's resolved config) applies to that request alone: result[i] is
+        what generate() returns for request i alone under ITS OWN config.  Its budget: the request's
+        `max_new_tokens`, then the budget its own config states, then the queue's.  `seed` (int): the request draws its uniforms from
+        torch.rand(budget_i, generator=torch.Generator(device).manual_seed(seed)) -- a function of (seed, budget) alone, so the request
+        is reproducible whatever else is in the queue.  model.last_inflight_stats counts `config_classes`, `sampler_rows`, `seeded`.
 
         The decode batch is `max_batch` slots; a slot whose request ended is refilled with the next request every `steps_per_sync` steps
         (visualcla/inflight.py, csrc/slots.hip).  result[i] is what generate() returns for request i alone at batch
         size 1.  With do_sample=True that holds for the function, not for the random stream: request i draws with its own uniforms,
-        torch.rand(budget_i) taken from the device generator in request order when the request is admitted.
+        torch.rand(budget_i) taken from the device generator in request order when the request is admitted (unless it carries a `seed`).
 
         Greedy, and every config the device sampler covers (repetition penalty, no-repeat-ngram, min_new_tokens, temperature, top-k <= 256,
-        top-p); everything else is refused by name.  model.last_inflight_stats describes the call.
+        top-p), per queue or per request; everything else is refused by name, in ONE message that names the requests
+        (`request 3, 7: num_beams=2`).  model.last_inflight_stats describes the call.
 
         share_prefix=True: the leading K/V rows that requests of the queue have in common -- a system prompt, the image slot of several
         questions about one image (compared by value) -- are computed once, kept in a pool of at most `prefix_pool_tokens` rows for the
@@ -1255,18 +1356,30 @@ class VisualCLAModel:
         gc = self._resolve_generation_config(generation_config, kwargs)
         t = self.config.text_config
         reqs = [self._inflight_request(i, r) for i, r in enumerate(requests)]
+        per_request = any(r["generation_config"] is not None for r in reqs)
+        gcs, cls, class_gcs = self._request_configs(gc, reqs) if per_request else ([gc] * len(reqs), [0] * len(reqs), [gc])
+        seeds = [r["seed"] for r in reqs]
         Q = self.config.visual_resampler_config["num_query_tokens"]
         lens = [int(r["ids"].numel()) + (Q if (self.image_at_head and r["px"] is not None) else 0) for r in reqs]
-        budgets = [int(r["max_new_tokens"]) if r["max_new_tokens"] is not None else new_token_budget(gc, T) for r, T in zip(reqs, lens)]
+        budgets = self._request_budgets(gc, reqs, gcs, lens)
         masked = []
         if share_prefix:
             with_mask = [i for i, r in enumerate(reqs) if r["am"] is not None]
             if with_mask:                                         # one copy back for the whole queue; an all-ones mask is no mask
                 lows = torch.stack([reqs[i]["am"].min() for i in with_mask]).tolist()
                 masked = [i for i, lo in zip(with_mask, lows) if not lo]
-        self._refuse_inflight_conflicts(gc, t["vocab_size"], bool(getattr(self, "_kv_fp8", False)),
-                                        max((min(b, t["max_position_embeddings"]) for b in budgets), default=0), kwargs,
-                                        share_prefix=bool(share_prefix), image_at_head=bool(self.image_at_head), masked_requests=masked)
+        if len(class_gcs) == 1:                                   # one config for the whole queue (the queue's, or the one every request brought)
+            self._refuse_inflight_conflicts(class_gcs[0], t["vocab_size"], bool(getattr(self, "_kv_fp8", False)),
+                                            max((min(b, t["max_position_embeddings"]) for b in budgets), default=0), kwargs,
+                                            share_prefix=bool(share_prefix), image_at_head=bool(self.image_at_head), masked_requests=masked)
+        else:
+            from .logits_processors import refuse_unsupported
+            refuse_unsupported(gc, kwargs)
+            self._refuse_per_request_conflicts(class_gcs, [[i for i, c in enumerate(cls) if c == k] for k in range(len(class_gcs))],
+                                               [min(b, t["max_position_embeddings"]) for b in budgets], t["vocab_size"],
+                                               bool(getattr(self, "_kv_fp8", False)), bool(share_prefix), bool(self.image_at_head), masked)
+        extra_stats = dict(config_classes=len(class_gcs), sampler_rows=sum(self._uses_sampler(g) for g in gcs),
+                           seeded=sum(sd is not None for sd in seeds))
         # raises for a prompt that leaves no room, by index, before any kernel runs
         sched = InflightScheduler(lens, budgets, [r["px"] is not None for r in reqs], max_batch, t["max_position_embeddings"], self.image_at_head,
                                   steps_per_sync, share_prefix=bool(share_prefix))
@@ -1276,15 +1389,19 @@ class VisualCLAModel:
             # max_batch = 1 or a single request: generate() per request (the persistent B = 1 step is the fast path there)
             out = []
             for i, r in enumerate(reqs):
-                toks = self.generate(input_ids=r["ids"][None], pixel_values=None if r["px"] is None else r["px"][None],
-                                     attention_mask=None if r["am"] is None else r["am"][None], generation_config=gc,
-                                     max_new_tokens=sched.budget[i], eos_token_id=gc.eos_token_id, use_graph=use_graph)[0].clone()   # (generate() may hand out its own buffer)
+                self._request_seed = seeds[i]                     # the private hook _draw_uniforms reads: no public argument of generate()
+                try:
+                    toks = self.generate(input_ids=r["ids"][None], pixel_values=None if r["px"] is None else r["px"][None],
+                                         attention_mask=None if r["am"] is None else r["am"][None], generation_config=gcs[i],
+                                         max_new_tokens=sched.budget[i], eos_token_id=gcs[i].eos_token_id, use_graph=use_graph)[0].clone()   # (generate() may hand out its own buffer)
+                finally:
+                    self._request_seed = None
                 out.append(toks)
                 sched.stats["tokens"] += int(toks.numel())
                 sched.stats["steps"] += int(toks.numel()) - 1
             sched.stats["slot_steps_active"] = sched.stats["slot_steps_total"] = sched.stats["steps"]
             sched.stats["admission_groups"] = len(reqs)
-            self.last_inflight_stats = dict(sched.stats)
+            self.last_inflight_stats = dict(sched.stats, **extra_stats)
             if share_prefix:                                      # one slot: nothing is alive to share with
                 self.last_inflight_stats.update(rows_reused=0, rows_computed=sum(lens), vision_runs=sum(r["px"] is not None for r in reqs), pool_entries=0,
                                                 pool_bytes=0)
@@ -1298,7 +1415,8 @@ class VisualCLAModel:
             side = self._side_stream
             side.wait_stream(cur_stream)
         with torch.cuda.device(self._device), torch.cuda.stream(side if side is not None else cur_stream):
-            out = self._inflight_on_stream(gc, reqs, sched, bool(use_graph), plan)
+            out = self._inflight_on_stream(class_gcs[0], reqs, sched, bool(use_graph), plan, gcs if len(class_gcs) > 1 else None, seeds)
+        self.last_inflight_stats.update(extra_stats)
         if side is not None:
             cur_stream.wait_stream(side)
         return out
@@ -1334,20 +1452,76 @@ class VisualCLAModel:
         prompts = [r["ids"].tolist() for r in reqs] if len({int(r["ids"].numel()) for r in reqs}) != 1 else torch.stack([r["ids"] for r in reqs]).tolist()
         return prefix.plan(prompts, keys, self._special_ids()[2] if with_px else None, slots, pool_rows)
 
-    def _inflight_on_stream(self, gc, reqs, sched, use_graph: bool, plan=None):
+    def _per_request_tables(self, gcs, sched):
+        """Requests under different configs: what the slots loop needs beside the queue-wide state.  eos_of[i] /
+        kw_of[i]: request i's eos list and its vcla_sample_row fields; eos_dev int32 [B, SLOT_MAX_EOS] and rows_dev uint8 [B, 64]: the
+        per-slot tables in device memory the captured step reads (rows_dev None: no request needs the sampler, the step is argmax + the
+        per-row eos lookup).  A greedy request is a record with top_k = 1 and the greedy flag."""
+        B = sched.slots
+        eos_of = [self._eos_list(g) for g in gcs]
+        kw_by_cfg: Dict[int, Optional[dict]] = {}
+        table = any(self._uses_sampler(g) for g in gcs)
+        kw_of = []
+        for i, g in enumerate(gcs):
+            if id(g) not in kw_by_cfg:
+                kw = None
+                if self._uses_sampler(g):
+                    kw = self._device_sampling(g, max(sched.budget[j] for j, h in enumerate(gcs) if h is g), 0)
+                    if kw is None:
+                        raise ValueError(f"generate_many: the generation config of request {i} does not map onto the device sampler")
+                kw_by_cfg[id(g)] = dict(kw or {}, greedy=not g.do_sample)
+            kw_of.append(kw_by_cfg[id(g)])
+        if table:
+            _lib.sample_row_table(kw_of)                          # range checks of every record, before any kernel runs
+        eos_dev = self._typed_buf("if_eos_rows", (B, _lib.SLOT_MAX_EOS), torch.int32)
+        eos_dev.fill_(-1)
+        rows_dev = None
+        if table:
+            rows_dev = self._typed_buf("if_sample_rows", (B, C.sizeof(_lib.SampleRow)), torch.uint8)
+            rows_dev.copy_(_lib.sample_row_bytes(_lib.sample_row_table([dict(greedy=True)] * B)))
+        return dict(eos_of=eos_of, kw_of=kw_of, eos_dev=eos_dev, rows_dev=rows_dev, do_sample=[bool(g.do_sample) for g in gcs])
+
+    def _inflight_fill_rows(self, per, requests, slots) -> None:
+        """admission: the table rows of the slots it fills, rewritten between two chunks of steps"""
+        sl = torch.tensor(list(slots), device=self._device)
+        per["eos_dev"][sl] = _lib.slot_eos_rows([per["eos_of"][i] for i in requests]).to(self._device)
+        if per["rows_dev"] is not None:
+            per["rows_dev"][sl] = _lib.sample_row_bytes(_lib.sample_row_table([per["kw_of"][i] for i in requests]), len(requests)).to(self._device)
+
+    def _inflight_first(self, logits, requests, sl, samp_kw, uni, per, hist):
+        """the first token of the requests whose prefill produced `logits` (row j = requests[j], slot sl[j]): the same selector as the steps,
+        at history length 0 -- argmax, the uniform sampler, or the table entry with the admitted requests' own records"""
+        G = len(requests)
+        u0 = uni[0, sl].view(1, G).contiguous() if uni is not None else None
+        if per is not None and per["rows_dev"] is not None:
+            rows = _lib.sample_row_bytes(_lib.sample_row_table([per["kw_of"][i] for i in requests]), G).to(self._device)
+            return _lib.sample_rows_table(logits, torch.zeros(G, dtype=torch.int32, device=self._device),
+                                          _lib.sample_args(uniforms=u0, history=hist), rows)
+        if samp_kw is None:
+            return _lib.argmax(logits)
+        return _lib.sample(logits, _lib.sample_args(uniforms=u0, **samp_kw), n_hist=0)
+
+    def _inflight_on_stream(self, gc, reqs, sched, use_graph: bool, plan=None, gcs=None, seeds=None):
+        """gcs None: one config `gc` for the whole queue.  Else gcs[i] is request i's config, there are at least two distinct ones, and the
+        step reads per-slot tables (_per_request_tables)."""
         import time
         from .logits_processors import min_token_floor
         lib = _lib.load()
         dev = self._device
         t = self.config.text_config
         B, ctx_max, cap = sched.slots, sched.ctx_max, sched.cap
-        eos = self._eos_list(gc)
+        seeds = seeds if seeds is not None else [None] * sched.n
+        per = self._per_request_tables(gcs, sched) if gcs is not None else None
+        eos = self._eos_list(gc) if per is None else []
         rp = gc.repetition_penalty if gc.repetition_penalty is not None else 1.0
         samp_kw = None
-        if gc.do_sample or rp != 1.0 or gc.no_repeat_ngram_size or (eos and min_token_floor(gc, 0) > 0):
+        if per is not None:
+            samp_kw = {} if per["rows_dev"] is not None else None   # the scalar fields of the shared block are ignored by the table entry
+        elif gc.do_sample or rp != 1.0 or gc.no_repeat_ngram_size or (eos and min_token_floor(gc, 0) > 0):
             samp_kw = self._device_sampling(gc, cap, 0)
             if samp_kw is None:
                 raise ValueError("generate_many: the generation config does not map onto the device sampler")
+        draws = [bool(gc.do_sample)] * sched.n if per is None else per["do_sample"]
         # ---- the slot table: one int32 vector (row_pos | count | hist_len | budget | summary) so that a boundary is ONE copy to the host
         W = _lib.SLOT_SUMMARY_WORDS
         st = self._typed_buf("if_state", (4 * B + W,), torch.int32)
@@ -1356,7 +1530,7 @@ class VisualCLAModel:
         hist = self._typed_buf("if_hist", (cap, B), torch.int64)
         cur = self._typed_buf("if_cur", (B,), torch.int64)
         cur.zero_()
-        uni = self._typed_buf("if_uni", (cap, B), torch.float32) if gc.do_sample else None
+        uni = self._typed_buf("if_uni", (cap, B), torch.float32) if any(draws) and samp_kw is not None else None
         H, d = t["num_attention_heads"], t["hidden_size"] // t["num_attention_heads"]
         kv = self._typed_buf("if_kv", (t["num_hidden_layers"], 2, B, H, ctx_max, d), self._dtype)
         km = self._typed_buf("if_km", (B, ctx_max), torch.int32)
@@ -1379,19 +1553,32 @@ class VisualCLAModel:
                     break
                 if uni is not None:                             # request i's own column of uniforms, drawn in request order
                     for i, b in sorted((i, b) for g in groups for i, b in zip(g.requests, g.slots)):
-                        uni[:sched.budget[i], b] = torch.rand(sched.budget[i], device=dev)
+                        if not draws[i]:
+                            continue                            # a greedy row of the table draws at 0
+                        if seeds[i] is None:
+                            uni[:sched.budget[i], b] = torch.rand(sched.budget[i], device=dev)
+                        else:                                   # a function of (seed, budget) alone, whatever else is in the queue
+                            uni[:sched.budget[i], b] = torch.rand(sched.budget[i], device=dev,
+                                                                  generator=torch.Generator(device=dev).manual_seed(int(seeds[i])))
                 for g in groups:
+                    if per is not None:
+                        self._inflight_fill_rows(per, g.requests, g.slots)
                     if g.ragged:
-                        self._inflight_admit_ragged(g, reqs, sched, eos, samp_kw, uni, kv, km, st, hist, cur, count_h, share)
+                        self._inflight_admit_ragged(g, reqs, sched, eos, samp_kw, uni, kv, km, st, hist, cur, count_h, share, per)
                     else:
-                        self._inflight_admit(g, reqs, sched, eos, samp_kw, uni, kv, km, st, hist, cur, count_h)
+                        self._inflight_admit(g, reqs, sched, eos, samp_kw, uni, kv, km, st, hist, cur, count_h, per)
             t1 = time.perf_counter()
             t_adm += t1 - t0
             if sched.finished:
                 break
             n = sched.steps_per_sync
-            _lib.check(lib.vcla_llama_decode_slots(self._ctx, C.byref(slots), n, kv.data_ptr(), ctx_max, km.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                   int(use_graph), C.byref(samp) if samp is not None else None, _lib.stream_ptr()))
+            if per is None:
+                _lib.check(lib.vcla_llama_decode_slots(self._ctx, C.byref(slots), n, kv.data_ptr(), ctx_max, km.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                       int(use_graph), C.byref(samp) if samp is not None else None, _lib.stream_ptr()))
+            else:
+                _lib.check(lib.vcla_llama_decode_slots_rows(self._ctx, C.byref(slots), n, kv.data_ptr(), ctx_max, km.data_ptr(), ws.data_ptr(),
+                                                            ws.numel(), int(use_graph), C.byref(samp) if samp is not None else None,
+                                                            per["eos_dev"].data_ptr(), _lib.ptr(per["rows_dev"]), _lib.stream_ptr()))
             host = st.tolist()                                  # the one synchronisation of the boundary: positions, counts, n_active
             pos_h, cnt_h = host[:B], host[B:2 * B]
             done = [b for b in range(B) if sched.slot_req[b] is not None and pos_h[b] < 0]
@@ -1409,7 +1596,7 @@ class VisualCLAModel:
                                             workspace_bytes=int(self._ws["extend_rows"].numel()) if "extend_rows" in self._ws else 0)
         return [torch.tensor(toks, dtype=torch.int64, device=dev) for toks in sched.ordered_results()]
 
-    def _inflight_admit(self, g, reqs, sched, eos, samp_kw, uni, kv, km, st, hist, cur, count_h) -> None:
+    def _inflight_admit(self, g, reqs, sched, eos, samp_kw, uni, kv, km, st, hist, cur, count_h, per=None) -> None:
         """One admission group through the request path of generate() as a left-padded batch (checks, vision stack, embedding splice, prefill
         into a private cache), then into its slots: K/V rows [0, T_group), the pad holes of the key mask, the first token, the slot state."""
         dev = self._device
@@ -1441,15 +1628,11 @@ class VisualCLAModel:
         km[sl] = 1
         if am2 is not None:
             km[sl, :Tg] = am2.to(torch.int32)
-        if samp_kw is None:
-            first = _lib.argmax(logits)
-        else:                                                   # the same selector as the steps, at history length 0
-            u0 = uni[0, sl].view(1, G).contiguous() if uni is not None else None
-            first = _lib.sample(logits, _lib.sample_args(uniforms=u0, **samp_kw), n_hist=0)
+        first = self._inflight_first(logits, g.requests, sl, samp_kw, uni, per, hist)
         first_h = first.tolist()                                # synchronises
         live = []
         for j, (i, b) in enumerate(zip(g.requests, g.slots)):
-            ended = first_h[j] in eos or sched.budget[i] == 1
+            ended = first_h[j] in (eos if per is None else per["eos_of"][i]) or sched.budget[i] == 1
             sched.started(b, first_h[j], ended)
             if not ended:
                 live.append((b, first_h[j], sched.budget[i]))
@@ -1467,7 +1650,7 @@ class VisualCLAModel:
 
     RAGGED_MAX_ROWS = 8192      # packed rows of one vcla_llama_extend_rows call (its workspace is sized for them); longer passes are cut
 
-    def _inflight_admit_ragged(self, g, reqs, sched, eos, samp_kw, uni, kv, km, st, hist, cur, count_h, share) -> None:
+    def _inflight_admit_ragged(self, g, reqs, sched, eos, samp_kw, uni, kv, km, st, hist, cur, count_h, share, per=None) -> None:
         """share_prefix=True: the requests admitted at one boundary, every one at position 0 of its slot.  In the passes of prefix.passes: copy
         the rows [0, P_i) each request reuses from the pool into its slot (one indexed copy per pass), run the vision stack over the images
         that are needed, then ONE vcla_llama_extend_rows over the rows [P_i, T_i) of all of them, written straight into the slots; the
@@ -1530,11 +1713,7 @@ class VisualCLAModel:
                     self._inflight_logits_tap.append((list(call), logits.detach().clone()))
                 sl = torch.tensor([slot_of[i] for i in call], device=dev)
                 km[sl] = 1
-                if samp_kw is None:
-                    first = _lib.argmax(logits)
-                else:                                           # the same selector as the steps, at history length 0
-                    u0 = uni[0, sl].view(1, len(call)).contiguous() if uni is not None else None
-                    first = _lib.sample(logits, _lib.sample_args(uniforms=u0, **samp_kw), n_hist=0)
+                first = self._inflight_first(logits, call, sl, samp_kw, uni, per, hist)
                 for i, tok in zip(call, first.tolist()):          # synchronises
                     first_of[i] = tok
             share["reused"] += sum(plan.P[i] for i in members)
@@ -1555,7 +1734,7 @@ class VisualCLAModel:
                     share["free"].extend(share["rows"].pop(s_))
         live = []
         for i, b in zip(g.requests, g.slots):
-            ended = first_of[i] in eos or sched.budget[i] == 1
+            ended = first_of[i] in (eos if per is None else per["eos_of"][i]) or sched.budget[i] == 1
             sched.started(b, first_of[i], ended)
             if not ended:
                 live.append((b, first_of[i], sched.budget[i], plan.T[i]))
