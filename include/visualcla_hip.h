@@ -668,6 +668,28 @@ size_t vcla_llama_extend_rows_workspace_bytes(const vcla_ctx* ctx, int M, int n_
 int vcla_llama_extend_rows(vcla_ctx* ctx, const void* inputs_embeds, const vcla_extend_seq* seqs, int n_seqs, void* kv_cache, int B_slots,
                            int ctx_max, float* logits, void* ws, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------- a prefix cache that outlives the call (blocks of 16 K / V rows)
+   The reference's generate() (models/visualcla/modeling_visualcla.py:349-391) starts every call from nothing.  A serving process keeps
+   the leading K / V rows of earlier prompts in a POOL of blocks of VCLA_KV_BLOCK_ROWS consecutive rows, addressed by content on the host,
+   and copies them into the slots of later requests (and the rows of new prompts out of their slots) with one launch per direction.
+   Additive entries; the ABI version stays 5. */
+#define VCLA_KV_BLOCK_ROWS 16
+
+typedef struct vcla_kv_block {
+    int32_t block;              /* pool block, 0 .. n_blocks - 1                                                                    */
+    int32_t slot;               /* sequence (slot) of the slots cache, 0 .. B_slots - 1                                             */
+    int32_t row0;               /* first of the 16 rows in the slot: a multiple of VCLA_KV_BLOCK_ROWS, row0 + 16 <= ctx_max          */
+} vcla_kv_block;
+
+/* Copies n_entries blocks between kv_slots [L][2][B_slots][H][ctx_max][d] and pool [n_blocks][L][2][H][16][d] (both `dtype`, 16-byte
+   aligned, d * esz a multiple of 16 bytes): to_pool != 0 reads rows [row0, row0 + 16) of `slot` into `block`, 0 writes `block` there.
+   Bytes outside the named destinations are not touched.  table: DEVICE memory, so the launcher cannot range-check it: the caller
+   validates it before the upload -- ranges, and DISTINCT destinations (two entries that write the same block, or the same rows of one
+   slot, race); several entries may read one source.  The kernel skips an entry that would leave either buffer.  n_entries = 0 is no
+   launch. */
+int vcla_kv_blocks_copy(void* kv_slots, void* pool, const vcla_kv_block* table, int n_entries, int L, int B_slots, int H, int ctx_max, int d,
+                        int n_blocks, int dtype, int to_pool, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

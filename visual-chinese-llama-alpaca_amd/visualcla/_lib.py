@@ -213,6 +213,32 @@ def extend_seqs(table):
     return arr, m
 
 
+KV_BLOCK_ROWS = 16          # VCLA_KV_BLOCK_ROWS: rows of one block of the prefix cache
+
+
+class KvBlock(C.Structure):
+    """vcla_kv_block: one entry of a vcla_kv_blocks_copy table, in device memory"""
+    _fields_ = [("block", C.c_int32), ("slot", C.c_int32), ("row0", C.c_int32)]
+
+
+def kv_block_table(entries, n_blocks: int, B_slots: int, ctx_max: int, to_pool: bool) -> torch.Tensor:
+    """[(block, slot, row0), ...] -> the table of vcla_kv_blocks_copy as an int32 host tensor [n, 3], ready for one copy to the device.
+    The launcher cannot range-check a table in device memory: block, slot, row0 (a multiple of 16, row0 + 16 <= ctx_max) and DISTINCT
+    destinations (blocks when to_pool, else (slot, row0)) are checked HERE, before the upload; ValueError names the entry."""
+    seen = set()
+    for k, (block, slot, row0) in enumerate(entries):
+        block, slot, row0 = int(block), int(slot), int(row0)
+        if not (0 <= block < n_blocks and 0 <= slot < B_slots):
+            raise ValueError(f"kv block entry {k}: block={block} (pool of {n_blocks}) slot={slot} (cache of {B_slots})")
+        if row0 < 0 or row0 % KV_BLOCK_ROWS or row0 + KV_BLOCK_ROWS > ctx_max:
+            raise ValueError(f"kv block entry {k}: row0={row0} must be a multiple of {KV_BLOCK_ROWS} with row0 + {KV_BLOCK_ROWS} <= ctx_max={ctx_max}")
+        dst = block if to_pool else (slot, row0)
+        if dst in seen:
+            raise ValueError(f"kv block entry {k}: destination {'block ' + str(block) if to_pool else 'slot %d rows %d..' % (slot, row0)} is written twice")
+        seen.add(dst)
+    return torch.tensor([[int(b), int(s), int(r)] for b, s, r in entries], dtype=torch.int32).view(-1, 3)
+
+
 SLOT_MAX_EOS = 8            # VCLA_SLOT_MAX_EOS
 SLOT_SUMMARY_WORDS = 4      # VCLA_SLOT_SUMMARY_WORDS: slots still active, the launch's arrival counter, two reserved words
 
@@ -300,6 +326,7 @@ SYMBOLS = {
     "vcla_attn_extend_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _i, _i, _vp, _sz, _vp]),
     "vcla_llama_extend_rows_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
     "vcla_llama_extend_rows": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _sz, _vp]),
+    "vcla_kv_blocks_copy": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -506,6 +533,20 @@ def sample_rows_table(logits, n_hist_rows, shared: SampleArgs, rows_dev, out=Non
     check(load().vcla_sample_rows_table(logits.data_ptr(), logits.stride(0), B, logits.shape[1], n_hist_rows.data_ptr(), C.byref(shared),
                                         rows_dev.data_ptr(), out.data_ptr(), stream_ptr()))
     return out
+
+
+def kv_blocks_copy(kv, pool, entries, to_pool: bool) -> None:
+    """vcla_kv_blocks_copy: kv [L, 2, B_slots, H, ctx_max, d], pool [n_blocks, L, 2, H, 16, d], both contiguous on the device in one dtype;
+    entries [(block, slot, row0), ...] in host memory, checked by kv_block_table before anything is written."""
+    assert kv.is_cuda and pool.is_cuda and kv.is_contiguous() and pool.is_contiguous() and kv.dtype == pool.dtype and kv.dim() == 6 and pool.dim() == 6
+    L, _, B_slots, H, ctx_max, d = kv.shape
+    assert tuple(pool.shape[1:]) == (L, 2, H, KV_BLOCK_ROWS, d), (tuple(pool.shape), tuple(kv.shape))
+    table = kv_block_table(entries, int(pool.shape[0]), B_slots, ctx_max, to_pool)
+    if not len(entries):
+        return
+    table = table.to(kv.device)
+    check(load().vcla_kv_blocks_copy(kv.data_ptr(), pool.data_ptr(), table.data_ptr(), len(entries), L, B_slots, H, ctx_max, d, int(pool.shape[0]),
+                                     dtype_code(kv.dtype), int(bool(to_pool)), stream_ptr()))
 
 
 def causal_lm_loss(logits, labels, ignore_index: int = -100):

@@ -654,6 +654,15 @@ class VisualCLAModel:
         from .session import Session
         return Session(self, max_tokens)
 
+    def new_prefix_cache(self, max_tokens: int = 8192):
+        """-> visualcla.prefix_cache.PrefixCache: leading K/V rows of earlier prompts, kept between generate_many(share_prefix=True,
+        prefix_cache=) calls in blocks of 16 rows (`cache.block_rows`) addressed by content.  The pool holds `max_tokens` rows
+        (`cache.nbytes`); the default 8192 is 4 GiB at the 7B shape in bf16 -- a judgement (a few hundred image slots and system prompts),
+        not a measurement.  `cache.stats` accumulates over calls; `cache.clear()` forgets the rows.  A context rebuild (a dtype switch,
+        enable_fp8_decode, set_image_size, a device move) empties it at the next call (`stats["invalidated"]`)."""
+        from .prefix_cache import PrefixCache
+        return PrefixCache(self, max_tokens)
+
     def _check_decode_status(self, B: int, ws: torch.Tensor) -> None:
         """At B = 1 the decode steps of the bf16 mode are persistent launches whose workgroups wait on each other with BOUNDED spins
         (csrc/decode_engine.hip); a wait that ran out leaves a code in the workspace and the tokens are garbage -- raise instead of returning
@@ -1324,7 +1333,7 @@ class VisualCLAModel:
 
     @torch.no_grad()
     def generate_many(self, requests, max_batch: int = 64, generation_config=None, steps_per_sync: int = 8, use_graph: Optional[bool] = None,
-                      share_prefix: bool = False, prefix_pool_tokens: Optional[int] = None, **kwargs):
+                      share_prefix: bool = False, prefix_pool_tokens: Optional[int] = None, prefix_cache=None, **kwargs):
         """In-flight batching over a queue: -> List[LongTensor [n_i]] in request order, the NEW tokens of every request, its eos included
         and nothing behind it.  requests: dicts with `input_ids` ([T] or [1, T]), optional `pixel_values`, `attention_mask`, `max_new_tokens`
         (default: the config's budget by generate()'s rules for that prompt), `generation_config`, `seed`.
@@ -1350,8 +1359,22 @@ class VisualCLAModel:
         duration of the call and copied into the slots of the requests that share them; only the rows behind are computed, and the vision
         stack runs once per distinct shared image (visualcla/prefix.py).  Every request sits un-padded at position 0
         of its slot.  Same results (fp32: the same ids; bf16: within rounding, copied and computed rows come from differently tiled
-        passes).  Refuses image_at_head=True and masked prompts."""
+        passes).  Refuses image_at_head=True and masked prompts.
+
+        prefix_cache (model.new_prefix_cache(), needs share_prefix=True): leading rows survive the call.  Every request first looks its
+        prompt up in the cache -- blocks of 16 rows addressed by content (ids and, behind the first placeholder, the image by value) --
+        and reuses max(cached rows, planned rows) from one of the two sources; after every admission pass the full 16-row blocks of the
+        admitted prompts are copied into the cache (visualcla/prefix_cache.py, csrc/kv_blocks.hip).  Same
+        results, under the terms of share_prefix.  With a cache a queue of one request (or max_batch=1) also takes the slots route.
+        last_inflight_stats gains cache_rows_reused, cache_blocks_inserted, cache_evictions, cache_insert_skipped."""
         from .inflight import InflightScheduler
+        from .prefix_cache import PrefixCache
+        if prefix_cache is not None:
+            if not share_prefix:
+                raise ValueError("generate_many: prefix_cache needs share_prefix=True (only the ragged admission of share_prefix places a request "
+                                 "un-padded at position 0, where cached rows fit)")
+            if not isinstance(prefix_cache, PrefixCache) or prefix_cache.model is not self:
+                raise ValueError("generate_many: prefix_cache was made by another model (model.new_prefix_cache() makes one for this model)")
         from .logits_processors import new_token_budget
         gc = self._resolve_generation_config(generation_config, kwargs)
         t = self.config.text_config
@@ -1385,8 +1408,9 @@ class VisualCLAModel:
                                   steps_per_sync, share_prefix=bool(share_prefix))
         if use_graph is None:
             use_graph = os.environ.get("VCLA_DECODE_GRAPH", "1") != "0"
-        if sched.slots == 1:
-            # max_batch = 1 or a single request: generate() per request (the persistent B = 1 step is the fast path there)
+        if sched.slots == 1 and (prefix_cache is None or not reqs):
+            # max_batch = 1 or a single request: generate() per request (the persistent B = 1 step is the fast path there).  With a prefix
+            # cache such a queue stays on the slots route, at one slot: generate() has no place for cached rows
             out = []
             for i, r in enumerate(reqs):
                 self._request_seed = seeds[i]                     # the private hook _draw_uniforms reads: no public argument of generate()
@@ -1406,7 +1430,13 @@ class VisualCLAModel:
                 self.last_inflight_stats.update(rows_reused=0, rows_computed=sum(lens), vision_runs=sum(r["px"] is not None for r in reqs), pool_entries=0,
                                                 pool_bytes=0)
             return out
-        plan = self._prefix_plan(reqs, sched.slots, prefix_pool_tokens) if share_prefix else None
+        plan = pstate = None
+        if share_prefix and prefix_cache is None:
+            plan = self._prefix_plan(reqs, sched.slots, prefix_pool_tokens)
+        elif share_prefix:                                        # the plan exactly as without a cache, then one lookup per request
+            keys, prompts = self._image_keys(reqs), self._prompt_lists(reqs)
+            plan = self._prefix_plan(reqs, sched.slots, prefix_pool_tokens, keys, prompts)
+            pstate = prefix_cache.begin(reqs, plan, keys, prompts, self._special_ids()[2] if any(k is not None for k in keys) else None)
         cur_stream = torch.cuda.current_stream(self._device)
         side = None
         if use_graph and cur_stream.cuda_stream == 0:          # graph capture is illegal on the legacy default stream (as generate())
@@ -1415,19 +1445,39 @@ class VisualCLAModel:
             side = self._side_stream
             side.wait_stream(cur_stream)
         with torch.cuda.device(self._device), torch.cuda.stream(side if side is not None else cur_stream):
-            out = self._inflight_on_stream(class_gcs[0], reqs, sched, bool(use_graph), plan, gcs if len(class_gcs) > 1 else None, seeds)
-        self.last_inflight_stats.update(extra_stats)
+            try:
+                out = self._inflight_on_stream(class_gcs[0], reqs, sched, bool(use_graph), plan, gcs if len(class_gcs) > 1 else None, seeds, pstate)
+            except BaseException:
+                if pstate is not None:                            # the index may name blocks whose copies were never enqueued
+                    prefix_cache.end()
+                    prefix_cache.clear()
+                raise
+            cache_stats = prefix_cache.end() if pstate is not None else {}
+        self.last_inflight_stats.update(extra_stats, **cache_stats)
         if side is not None:
             cur_stream.wait_stream(side)
         return out
 
-    def _prefix_plan(self, reqs, slots: int, pool_rows: Optional[int]):
-        """the prefix plan of a queue (visualcla/prefix.py) from its ids and images.  Images are compared BY VALUE, as the vision stack sees
-        them (model dtype), inside this pass: one fingerprint per image (a launch over the stacked images, one copy back) buckets them, one
-        row-wise comparison of every image with the first of its bucket confirms (a second copy back); the same tensor object needs neither."""
+    def _prefix_plan(self, reqs, slots: int, pool_rows: Optional[int], keys=None, prompts=None):
+        """the prefix plan of a queue (visualcla/prefix.py) from its ids and images (keys / prompts: _image_keys / _prompt_lists of the
+        queue, when the caller needs them too)"""
         from . import prefix
         if pool_rows is not None and int(pool_rows) < 0:
             raise ValueError(f"prefix_pool_tokens must be >= 0 (got {pool_rows})")
+        keys = self._image_keys(reqs) if keys is None else keys
+        prompts = self._prompt_lists(reqs) if prompts is None else prompts
+        return prefix.plan(prompts, keys, self._special_ids()[2] if any(k is not None for k in keys) else None, slots, pool_rows)
+
+    @staticmethod
+    def _prompt_lists(reqs):
+        """the ids of every request as host lists (one copy back when the prompts have one length)"""
+        return [r["ids"].tolist() for r in reqs] if len({int(r["ids"].numel()) for r in reqs}) != 1 else torch.stack([r["ids"] for r in reqs]).tolist()
+
+    def _image_keys(self, reqs):
+        """one key per request, None without an image, equal for equal images: the index of the first request that carries the image.
+        Images are compared BY VALUE, as the vision stack sees them (model dtype), inside this pass: one fingerprint per image (a launch
+        over the stacked images, one copy back) buckets them, one row-wise comparison of every image with the first of its bucket
+        confirms (a second copy back); the same tensor object needs neither."""
         keys: List[Optional[int]] = [None] * len(reqs)
         with_px = [i for i, r in enumerate(reqs) if r["px"] is not None]
         by_obj: Dict[int, int] = {}
@@ -1449,8 +1499,7 @@ class VisualCLAModel:
                 keys[i] = members[cand[k]] if same[k] else i      # (a fingerprint collision of different images: a key of its own)
         for i in with_px:
             keys[i] = keys[by_obj[id(reqs[i]["px"])]]
-        prompts = [r["ids"].tolist() for r in reqs] if len({int(r["ids"].numel()) for r in reqs}) != 1 else torch.stack([r["ids"] for r in reqs]).tolist()
-        return prefix.plan(prompts, keys, self._special_ids()[2] if with_px else None, slots, pool_rows)
+        return keys
 
     def _per_request_tables(self, gcs, sched):
         """Requests under different configs: what the slots loop needs beside the queue-wide state.  eos_of[i] /
@@ -1501,9 +1550,9 @@ class VisualCLAModel:
             return _lib.argmax(logits)
         return _lib.sample(logits, _lib.sample_args(uniforms=u0, **samp_kw), n_hist=0)
 
-    def _inflight_on_stream(self, gc, reqs, sched, use_graph: bool, plan=None, gcs=None, seeds=None):
+    def _inflight_on_stream(self, gc, reqs, sched, use_graph: bool, plan=None, gcs=None, seeds=None, pstate=None):
         """gcs None: one config `gc` for the whole queue.  Else gcs[i] is request i's config, there are at least two distinct ones, and the
-        step reads per-slot tables (_per_request_tables)."""
+        step reads per-slot tables (_per_request_tables).  pstate: the call's state of a prefix cache (PrefixCache.begin), or None."""
         import time
         from .logits_processors import min_token_floor
         lib = _lib.load()
@@ -1544,7 +1593,10 @@ class VisualCLAModel:
         if plan is not None:                                    # the prefix pool of this call: [rows, L, 2, H, d], 2 L H d elements per row
             n_rows = min(plan.pool_rows, plan.peak_pool_rows)
             pool = torch.empty(n_rows, t["num_hidden_layers"], 2, H, d, dtype=self._dtype, device=dev)
-            share = dict(plan=plan, pool=pool, free=list(range(n_rows - 1, -1, -1)), rows={}, reused=0, computed=0, vision=0, passes=0, calls=0)
+            share = dict(plan=plan, pool=pool, free=list(range(n_rows - 1, -1, -1)), rows={}, reused=0, computed=0, vision=0, passes=0, calls=0,
+                         P=plan.P, vis=plan.vision_needed, pstate=pstate)
+            if pstate is not None:                              # rows and vision runs as the cache and the plan combine (prefix_cache.combine)
+                share.update(P=pstate["P"], vis=pstate["vision"])
         while not sched.finished:
             t0 = time.perf_counter()
             while True:                                         # a request whose first token ends it frees its slot within the boundary
@@ -1659,6 +1711,8 @@ class VisualCLAModel:
         dev = self._device
         B = sched.slots
         plan, pool = share["plan"], share["pool"]
+        P, vis_needed, pstate = share["P"], share["vis"], share["pstate"]   # without a prefix cache: plan.P, plan.vision_needed, None
+        cached = pstate["from_cache"] if pstate is not None else [False] * len(P)
         slot_of = dict(zip(g.requests, g.slots))
         Q = self.config.visual_resampler_config["num_query_tokens"]
         first_of: Dict[int, int] = {}
@@ -1670,14 +1724,16 @@ class VisualCLAModel:
             return pi, si, ri
         for members in prefix.passes(plan, g.requests):
             share["passes"] += 1
-            reads = [(slot_of[i], 0, share["rows"][plan.source[i]][:plan.P[i]]) for i in members if plan.P[i] > 0]
+            reads = [(slot_of[i], 0, share["rows"][plan.source[i]][:P[i]]) for i in members if P[i] > 0 and not cached[i]]
             if reads:
                 pi, si, ri = index(reads)
                 kv[:, :, si, :, ri] = pool[pi]
+            if pstate is not None:                              # the rows the prefix cache holds: its blocks into the slots, one launch
+                _lib.kv_blocks_copy(kv, pstate["cache"].pool, pstate["cache"].read_entries(pstate, members, slot_of), to_pool=False)
             # ---- embeddings of whole prompts, by classes of equal (length, image, vision needed): one check and one splice per class
             classes: Dict[tuple, List[int]] = {}
             for i in members:
-                classes.setdefault((int(reqs[i]["ids"].numel()), reqs[i]["px"] is not None, plan.vision_needed[i]), []).append(i)
+                classes.setdefault((int(reqs[i]["ids"].numel()), reqs[i]["px"] is not None, vis_needed[i]), []).append(i)
             emb_of: Dict[int, torch.Tensor] = {}
             for (T, has_px, vis), cls in classes.items():
                 ids = torch.stack([reqs[i]["ids"] for i in cls])
@@ -1688,11 +1744,11 @@ class VisualCLAModel:
                     share["vision"] += len(cls)
                 embeds, _ = self._embed(ids, img, img_pos if vis else None)
                 for j, i in enumerate(cls):
-                    emb_of[i] = embeds[j, plan.P[i]:]
+                    emb_of[i] = embeds[j, P[i]:]
             # ---- the rows behind the shared prefixes, cut into calls of at most RAGGED_MAX_ROWS rows (a block the kernel does not take goes alone)
             calls, cur_call, m = [], [], 0
             for i in members:
-                r = plan.T[i] - plan.P[i]
+                r = plan.T[i] - P[i]
                 alone = r > _lib.EXTEND_MAX_ROWS
                 if cur_call and (alone or m + r > self.RAGGED_MAX_ROWS):
                     calls.append(cur_call)
@@ -1705,7 +1761,7 @@ class VisualCLAModel:
             if cur_call:
                 calls.append(cur_call)
             for call in calls:
-                table = [(slot_of[i], plan.P[i], plan.T[i] - plan.P[i]) for i in call]
+                table = [(slot_of[i], P[i], plan.T[i] - P[i]) for i in call]
                 logits = self._extend_rows(torch.cat([emb_of[i] for i in call]), table, kv,
                                            ws_for=(min(self.RAGGED_MAX_ROWS, B * max(plan.T)), B))
                 share["calls"] += 1
@@ -1716,8 +1772,8 @@ class VisualCLAModel:
                 first = self._inflight_first(logits, call, sl, samp_kw, uni, per, hist)
                 for i, tok in zip(call, first.tolist()):          # synchronises
                     first_of[i] = tok
-            share["reused"] += sum(plan.P[i] for i in members)
-            share["computed"] += sum(plan.T[i] - plan.P[i] for i in members)
+            share["reused"] += sum(P[i] for i in members)
+            share["computed"] += sum(plan.T[i] - P[i] for i in members)
             # ---- the creators of this pass leave their rows in the pool; entries whose last reader this pass held are released
             made = []
             for i in members:
@@ -1732,6 +1788,8 @@ class VisualCLAModel:
                 s_ = plan.source[i]
                 if s_ is not None and plan.entries[s_].last_reader == i:
                     share["free"].extend(share["rows"].pop(s_))
+            if pstate is not None:                              # the members' full blocks that the prefix cache lacks: out of the slots, one launch
+                _lib.kv_blocks_copy(kv, pstate["cache"].pool, pstate["cache"].insert_entries(pstate, members, slot_of), to_pool=True)
         live = []
         for i, b in zip(g.requests, g.slots):
             ended = first_of[i] in (eos if per is None else per["eos_of"][i]) or sched.budget[i] == 1
