@@ -690,6 +690,53 @@ typedef struct vcla_kv_block {
 int vcla_kv_blocks_copy(void* kv_slots, void* pool, const vcla_kv_block* table, int n_entries, int L, int B_slots, int H, int ctx_max, int d,
                         int n_blocks, int dtype, int to_pool, void* stream);
 
+/* ---------------------------------------------------------------- per-token log-probabilities and scored continuations (slots)
+   HF hands the distribution of every step back through `output_logits` / `output_scores` and compute_transition_scores
+   (hf:generation/utils.py, the per-token loop reached from models/visualcla/modeling_visualcla.py:382-391): log_softmax of the step's
+   [B, V] logits, gathered at the token taken.  Here the slots step computes, per active row and on the RAW fp32 logits of the lm_head
+   (before any processor or warper), the log-probability of the token taken and the k most likely tokens; a row may also be
+   TEACHER-FORCED: it takes a given id instead of the selected one (scoring a continuation = the labels of a forward pass, one token per
+   step on the slot's own cache).  Additive entries; the ABI version stays 5. */
+#define VCLA_LOGPROB_MAX_K 20
+typedef struct vcla_logprob_args {
+    int k;                       /* 0 .. VCLA_LOGPROB_MAX_K                                                                          */
+    float*   token_logprob;      /* [hist_cap, B] step-major, the layout of vcla_slot_args.history                                  */
+    int64_t* top_ids;            /* [hist_cap, B, k] (NULL when k == 0)                                                              */
+    float*   top_logprobs;       /* [hist_cap, B, k]                                                                                 */
+    const int64_t* forced;       /* [hist_cap, B]: >= 0: the id the slot takes at that step; < 0: the selected one.  NULL: none      */
+} vcla_logprob_args;
+
+/* The stats pass, BEFORE the selector: for every row b with h = n_hist_rows[b] >= 0, over logits[b][0 .. V) (fp32, row stride ld >= V;
+   columns at or behind V are never read): lse[b] = max + log(sum exp(x - max)) in fp32 (lse: device float [B], read by
+   vcla_logprob_pick), and at [h][b] of args->top_ids / top_logprobs the k largest entries in the order (value descending, id ascending
+   -- the tie rule of vcla_argmax) with top_logprobs = value - lse.  Rows with h < 0 are skipped, their outputs and lse[b] untouched;
+   h >= hist_cap writes lse[b] only.  copy non-NULL ([B, copy_ld >= V] fp32): the V columns of every served row are also written there
+   -- the buffer a sampler that modifies its input then consumes, so that `logits` stays raw for the gather.  One 1024-thread workgroup
+   per row with the row in registers: V <= VCLA_SAMPLE_MAX_VOCAB.  args->token_logprob must be set (one struct serves both passes);
+   neither it nor args->forced is touched here. */
+int vcla_logprob_rows(const float* logits, int64_t ld, int B, int V, const int32_t* n_hist_rows, int hist_cap, const vcla_logprob_args* args,
+                      float* lse, float* copy, int64_t copy_ld, void* stream);
+
+/* The gather, AFTER the selector and before vcla_slot_step: for every row b with 0 <= h = n_hist_rows[b] < hist_cap: if args->forced holds
+   an id in [0, V) at [h][b], ids[b] = that id; then args->token_logprob[h][b] = logits[b][ids[b]] - lse[b].  `logits` are the RAW
+   logits the stats pass read (not the buffer a sampler worked on). */
+int vcla_logprob_pick(const float* logits, int64_t ld, int B, int V, const int32_t* n_hist_rows, int hist_cap, const vcla_logprob_args* args,
+                      const float* lse, int64_t* ids, void* stream);
+
+/* Bytes vcla_llama_decode_slots_logprobs needs BEHIND the vcla_llama_workspace_bytes(ctx, B, 1) of its workspace when logprobs is
+   non-NULL: lse [B] and, with_copy (a sampler runs), the [B, V] copy the sampler consumes. */
+size_t vcla_logprob_scratch_bytes(int B, int V, int with_copy);
+
+/* vcla_llama_decode_slots_rows plus per-token log-probabilities: logprobs NULL is that function.  Otherwise every step runs
+   vcla_logprob_rows on the step's logits at slots->hist_len (required) before the selector -- with `sampling`, the sampler consumes the
+   copy and its arithmetic is bit for bit what it is without logprobs -- and vcla_logprob_pick behind it, so the bookkeeping (eos
+   included) acts on the id actually taken.  ws_bytes >= vcla_llama_workspace_bytes(ctx, B, 1) + vcla_logprob_scratch_bytes(B, vocab,
+   sampling != NULL).  The bytes of *logprobs are part of the graph key: a capture without logprobs is never replayed for a call with
+   them, nor the reverse. */
+int vcla_llama_decode_slots_logprobs(vcla_ctx* ctx, const vcla_slot_args* slots, int n_steps, void* kv_cache, int ctx_max,
+                                     const int32_t* key_mask, void* ws, size_t ws_bytes, int use_graph, const vcla_sample_args* sampling,
+                                     const int32_t* eos_rows, const vcla_sample_row* rows, const vcla_logprob_args* logprobs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

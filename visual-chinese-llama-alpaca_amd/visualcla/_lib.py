@@ -266,6 +266,32 @@ def slot_args(eos_ids, row_pos, count, budget, hist_len, history, cur, summary):
     return a
 
 
+LOGPROB_MAX_K = 20          # VCLA_LOGPROB_MAX_K
+
+
+class LogprobArgs(C.Structure):
+    _fields_ = [("k", C.c_int), ("token_logprob", C.c_void_p), ("top_ids", C.c_void_p), ("top_logprobs", C.c_void_p), ("forced", C.c_void_p)]
+
+
+def logprob_args(k, token_logprob, top_ids=None, top_logprobs=None, forced=None):
+    """vcla_logprob_args over device tensors: token_logprob float32 [cap, B], top_ids int64 / top_logprobs float32 [cap, B, k] (None when
+    k == 0), forced int64 [cap, B] or None"""
+    k = int(k)
+    if not 0 <= k <= LOGPROB_MAX_K:
+        raise ValueError(f"logprobs={k} outside 0..{LOGPROB_MAX_K}")
+    if k and (top_ids is None or top_logprobs is None):
+        raise ValueError(f"logprobs={k} needs top_ids and top_logprobs")
+    for name, x, dt in (("token_logprob", token_logprob, torch.float32), ("top_ids", top_ids, torch.int64),
+                        ("top_logprobs", top_logprobs, torch.float32), ("forced", forced, torch.int64)):
+        if x is not None and (x.dtype != dt or not x.is_contiguous()):
+            raise ValueError(f"logprob_args: {name} must be a contiguous {dt} tensor")
+    a = LogprobArgs()
+    a.k = k
+    a.token_logprob, a.forced = ptr(token_logprob), ptr(forced)
+    a.top_ids, a.top_logprobs = (ptr(top_ids), ptr(top_logprobs)) if k else (None, None)
+    return a
+
+
 # every symbol include/visualcla_hip.h declares: name -> (restype, argtypes)
 _vp, _i, _i64, _f, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
 SYMBOLS = {
@@ -327,6 +353,11 @@ SYMBOLS = {
     "vcla_llama_extend_rows_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
     "vcla_llama_extend_rows": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _sz, _vp]),
     "vcla_kv_blocks_copy": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "vcla_logprob_rows": (_i, [_vp, _i64, _i, _i, _vp, _i, C.POINTER(LogprobArgs), _vp, _vp, _i64, _vp]),
+    "vcla_logprob_pick": (_i, [_vp, _i64, _i, _i, _vp, _i, C.POINTER(LogprobArgs), _vp, _vp, _vp]),
+    "vcla_logprob_scratch_bytes": (_sz, [_i, _i, _i]),
+    "vcla_llama_decode_slots_logprobs": (_i, [_vp, C.POINTER(SlotArgs), _i, _vp, _i, _vp, _vp, _sz, _i, C.POINTER(SampleArgs), _vp, _vp,
+                                              C.POINTER(LogprobArgs), _vp]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -533,6 +564,37 @@ def sample_rows_table(logits, n_hist_rows, shared: SampleArgs, rows_dev, out=Non
     check(load().vcla_sample_rows_table(logits.data_ptr(), logits.stride(0), B, logits.shape[1], n_hist_rows.data_ptr(), C.byref(shared),
                                         rows_dev.data_ptr(), out.data_ptr(), stream_ptr()))
     return out
+
+
+def logprob_rows(logits, n_hist_rows, args: LogprobArgs, hist_cap: int, lse=None, copy=None):
+    """vcla_logprob_rows: logits [B, V] fp32 (row stride >= V, not modified), n_hist_rows int32 [B] -> lse float32 [B]; the top-k outputs
+    go to the buffers of `args` at [n_hist_rows[b], b].  copy ([B, >= V] fp32): also receives the rows (what a sampler then consumes)."""
+    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1:
+        raise ValueError("logprob_rows: logits must be a [B, V] float32 tensor with unit column stride")
+    if n_hist_rows.dtype != torch.int32 or n_hist_rows.numel() != logits.shape[0]:
+        raise ValueError("logprob_rows: n_hist_rows must be int32 [B]")
+    B, V = logits.shape
+    if lse is None:
+        lse = torch.empty(B, dtype=torch.float32, device=logits.device)
+    if copy is not None and (copy.dtype != torch.float32 or copy.shape[0] != B or copy.shape[1] < V or copy.stride(1) != 1):
+        raise ValueError("logprob_rows: copy must be a [B, >= V] float32 tensor")
+    check(load().vcla_logprob_rows(logits.data_ptr(), logits.stride(0), B, V, n_hist_rows.data_ptr(), int(hist_cap), C.byref(args), lse.data_ptr(),
+                                   ptr(copy), copy.stride(0) if copy is not None else 0, stream_ptr()))
+    return lse
+
+
+def logprob_pick(logits, n_hist_rows, args: LogprobArgs, hist_cap: int, lse, ids):
+    """vcla_logprob_pick: the RAW logits [B, V] of logprob_rows, its lse, ids int64 [B] (a forced id replaces the selected one in place)
+    -> ids; args.token_logprob[n_hist_rows[b], b] = raw[b, ids[b]] - lse[b]"""
+    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1:
+        raise ValueError("logprob_pick: logits must be a [B, V] float32 tensor with unit column stride")
+    B, V = logits.shape
+    if ids.dtype != torch.int64 or ids.numel() != B or lse.dtype != torch.float32 or lse.numel() != B or n_hist_rows.dtype != torch.int32 or \
+            n_hist_rows.numel() != B:
+        raise ValueError("logprob_pick: ids int64 [B], lse float32 [B] and n_hist_rows int32 [B] are required")
+    check(load().vcla_logprob_pick(logits.data_ptr(), logits.stride(0), B, V, n_hist_rows.data_ptr(), int(hist_cap), C.byref(args), lse.data_ptr(),
+                                   ids.data_ptr(), stream_ptr()))
+    return ids
 
 
 def kv_blocks_copy(kv, pool, entries, to_pool: bool) -> None:

@@ -10,9 +10,25 @@ compare the kernel with it.
 """
 from __future__ import annotations
 
-from collections import deque
+from collections import deque, namedtuple
 from dataclasses import dataclass, field
 from typing import Callable, Dict, List, Optional, Sequence
+
+# result[i] of generate_many(..., logprobs=k): tokens int64 [n], logprobs float32 [n] (log_softmax of the RAW logits of step t at
+# tokens[t]), top_ids int64 [n, k] / top_logprobs float32 [n, k] (the k most likely tokens of that distribution, descending, ties by
+# the lower id)
+RequestOutput = namedtuple("RequestOutput", ["tokens", "logprobs", "top_ids", "top_logprobs"])
+
+LOGPROB_MAX_K = 20          # VCLA_LOGPROB_MAX_K
+
+
+def check_logprobs(logprobs) -> Optional[int]:
+    """the `logprobs` argument of generate_many / chat_many: None, or an int in 0..20 (bool is refused)"""
+    if logprobs is None:
+        return None
+    if isinstance(logprobs, bool) or not isinstance(logprobs, int) or not 0 <= logprobs <= LOGPROB_MAX_K:
+        raise ValueError(f"logprobs must be None or an integer in 0..{LOGPROB_MAX_K} (got {logprobs!r})")
+    return int(logprobs)
 
 
 def round_up(x: int, m: int) -> int:
@@ -63,10 +79,16 @@ class InflightScheduler:
 
     share_prefix: admission is RAGGED (visualcla/prefix.py) -- the requests admitted at one boundary form ONE group
     whatever their lengths and images, nobody is padded, and request i decodes from its own T_i.  Who is admitted when, and into which
-    slot, does not change."""
+    slot, does not change.
+
+    logprobs (k or None): with a value every finished request also carries its per-token arrays (`extra` of started / `extras_of` of
+    after_chunk: (logprobs [n], top_ids [n][k], top_logprobs [n][k])), and ordered_results() returns RequestOutput tuples.  targets[i]
+    (a list of ids, or None): request i is teacher-forced -- its budget is len(targets[i]), whatever budgets[i] says, and a target that
+    does not fit under max_position_embeddings raises instead of being clipped."""
 
     def __init__(self, prompt_lens: Sequence[int], budgets: Sequence[int], has_image: Sequence[bool], max_batch: int,
-                 max_position_embeddings: int, image_at_head: bool = False, steps_per_sync: int = 8, share_prefix: bool = False):
+                 max_position_embeddings: int, image_at_head: bool = False, steps_per_sync: int = 8, share_prefix: bool = False,
+                 logprobs: Optional[int] = None, targets: Optional[Sequence[Optional[Sequence[int]]]] = None):
         if max_batch < 1:
             raise ValueError(f"max_batch must be at least 1 (got {max_batch})")
         if steps_per_sync < 1:
@@ -76,9 +98,19 @@ class InflightScheduler:
         self.has_image = [bool(x) for x in has_image]
         self.max_pos = int(max_position_embeddings)
         self.budget: List[int] = []
+        self.logprobs = check_logprobs(logprobs)
+        self.targets: List[Optional[List[int]]] = [None if x is None else [int(v) for v in x] for x in (targets or [None] * len(prompt_lens))]
+        if len(self.targets) != len(prompt_lens):
+            raise ValueError(f"targets has {len(self.targets)} entries for {len(prompt_lens)} requests")
+        if self.logprobs is None and any(x is not None for x in self.targets):
+            raise ValueError("targets need logprobs")
+        budgets = [b if x is None else len(x) for b, x in zip(budgets, self.targets)]
         for i, (t, b) in enumerate(zip(self.T, budgets)):
             if self.max_pos - t <= 0:
                 raise ValueError(f"request {i}: prompt of {t} tokens leaves no room under max_position_embeddings={self.max_pos}")
+            if self.targets[i] is not None and not 1 <= b <= self.max_pos - t:
+                raise ValueError(f"request {i}: target_ids of {b} tokens (at least 1, and at most the {self.max_pos - t} positions its prompt "
+                                 f"leaves under max_position_embeddings={self.max_pos})")
             if int(b) < 1:
                 raise ValueError(f"request {i}: max_new_tokens must be at least 1 (got {b})")
             self.budget.append(min(int(b), self.max_pos - t))
@@ -91,6 +123,7 @@ class InflightScheduler:
         self.queue = deque(range(self.n))
         self.slot_req: List[Optional[int]] = [None] * self.slots
         self.results: Dict[int, List[int]] = {}
+        self.extras: Dict[int, tuple] = {}                       # logprobs: request -> (logprobs, top_ids, top_logprobs)
         self.decode_from: Dict[int, int] = {}                    # request -> T of its admission group = the position its slot decoded from
         self.stats = {"requests": self.n, "slots": self.slots, "steps": 0, "tokens": 0, "admission_groups": 0, "slot_steps_active": 0,
                       "slot_steps_total": 0}
@@ -134,25 +167,29 @@ class InflightScheduler:
         self.stats["admission_groups"] += len(groups)
         return groups
 
-    def _finish(self, b: int, tokens: Sequence[int]) -> None:
+    def _finish(self, b: int, tokens: Sequence[int], extra=None) -> None:
         i = self.slot_req[b]
         if i is None or i in self.results:
             raise ValueError(f"slot {b}: no running request to finish")
+        if self.logprobs is not None:
+            if extra is None or any(len(x) != len(tokens) for x in extra):
+                raise ValueError(f"slot {b}: request {i} finished without one log-probability per token")
+            self.extras[i] = tuple(list(x) for x in extra)
         self.results[i] = [int(t) for t in tokens]
         self.stats["tokens"] += len(tokens)
         self.slot_req[b] = None
 
-    def started(self, b: int, first_token: int, ended: bool) -> None:
+    def started(self, b: int, first_token: int, ended: bool, extra=None) -> None:
         """The first token of slot b's request came out of its prefill.  ended (an eos, or a budget of 1): the request is complete and
-        never occupies the slot past this boundary."""
+        never occupies the slot past this boundary.  extra (logprobs): the arrays of that one token."""
         if ended:
-            self._finish(b, [first_token])
+            self._finish(b, [first_token], extra)
 
     # ------------------------------------------------------------------ after a chunk of steps
     def after_chunk(self, n_steps: int, row_pos: Sequence[int], count: Sequence[int], tokens_of: Callable[[int, int], Sequence[int]],
-                    count_before: Optional[Sequence[int]] = None) -> List[int]:
-        """n_steps steps ran.  Slots whose request finished (row_pos < 0) are harvested -- tokens_of(slot, n) returns the slot's n tokens
-        -- and freed.  Returns them."""
+                    count_before: Optional[Sequence[int]] = None, extras_of: Optional[Callable[[int, int], tuple]] = None) -> List[int]:
+        """n_steps steps ran.  Slots whose request finished (row_pos < 0) are harvested -- tokens_of(slot, n) returns the slot's n tokens,
+        extras_of(slot, n) (logprobs) its per-token arrays -- and freed.  Returns them."""
         self.stats["steps"] += n_steps
         self.stats["slot_steps_total"] += n_steps * self.slots
         done = []
@@ -162,7 +199,7 @@ class InflightScheduler:
             if count_before is not None:
                 self.stats["slot_steps_active"] += int(count[b]) - int(count_before[b])
             if row_pos[b] < 0:
-                self._finish(b, tokens_of(b, int(count[b])))
+                self._finish(b, tokens_of(b, int(count[b])), extras_of(b, int(count[b])) if extras_of is not None else None)
                 done.append(b)
         return done
 
@@ -174,10 +211,13 @@ class InflightScheduler:
     def finished(self) -> bool:
         return not self.queue and self.running == 0
 
-    def ordered_results(self) -> List[List[int]]:
+    def ordered_results(self):
+        """the tokens of every request in request order; with logprobs, RequestOutput tuples (of lists) instead"""
         if len(self.results) != self.n:
             raise ValueError(f"{self.n - len(self.results)} requests have not finished")
-        return [self.results[i] for i in range(self.n)]
+        if self.logprobs is None:
+            return [self.results[i] for i in range(self.n)]
+        return [RequestOutput(self.results[i], *self.extras[i]) for i in range(self.n)]
 
 
 def step_bound(budgets: Sequence[int], slots: int, steps_per_sync: int) -> float:
@@ -195,20 +235,32 @@ def static_batch_steps(budgets: Sequence[int], slots: int) -> int:
 
 
 def simulate(budgets: Sequence[int], slots: int, steps_per_sync: int, eos_at: Optional[Dict[int, int]] = None, prompt_lens=None, has_image=None,
-             max_position_embeddings: int = 1 << 20, image_at_head: bool = False, share_prefix: bool = False):
+             max_position_embeddings: int = 1 << 20, image_at_head: bool = False, share_prefix: bool = False, logprobs: Optional[int] = None,
+             targets=None):
     """Drives a scheduler with the host model of the slot step and a stepper that emits token (request, k) = 1000 * request + k, or the
-    eos id 0 as request i's eos_at[i]-th token.  Returns (scheduler, log of (boundary, slot, request) admissions)."""
+    eos id 0 as request i's eos_at[i]-th token.  Returns (scheduler, log of (boundary, slot, request) admissions).
+    logprobs / targets: the scheduler's; a forced request emits its targets instead, and token t of request i scores
+    -(i + t / 1000) with top ids [t * 10 + r] and top logprobs [-(i + r)] (a stand-in for the device buffers)."""
     n = len(budgets)
     eos_at = eos_at or {}
     sch = InflightScheduler(prompt_lens or [4] * n, budgets, has_image or [False] * n, slots, max_position_embeddings, image_at_head, steps_per_sync,
-                            share_prefix)
+                            share_prefix, logprobs, targets)
     B = sch.slots
     row_pos, count, bud, cur = [-1] * B, [0] * B, [0] * B, [0] * B
     history = [[0] * B for _ in range(sch.cap)]
     log = []
+    K = sch.logprobs or 0
 
     def tok(i, k):
+        if sch.targets[i] is not None:
+            return sch.targets[i][k - 1]
         return 0 if eos_at.get(i) == k else 1000 * (i + 1) + k
+
+    def extra(i, m):                                             # what the device buffers of request i hold for its first m tokens
+        if sch.logprobs is None:
+            return None
+        return ([-(i + t / 1000) for t in range(m)], [[t * 10 + r for r in range(K)] for t in range(m)],
+                [[-float(i + r) for r in range(K)] for t in range(m)])
     boundary = 0
     while not sch.finished:
         while True:                                              # a request that ends at its first token frees its slot at once
@@ -220,7 +272,7 @@ def simulate(budgets: Sequence[int], slots: int, steps_per_sync: int, eos_at: Op
                     log.append((boundary, b, i))
                     first = tok(i, 1)
                     ended = first == 0 or sch.budget[i] == 1
-                    sch.started(b, first, ended)
+                    sch.started(b, first, ended, extra(i, 1))
                     if not ended:
                         row_pos[b], count[b], bud[b], cur[b] = sch.decode_from[i], 1, sch.budget[i], first
                         history[0][b] = first
@@ -230,6 +282,7 @@ def simulate(budgets: Sequence[int], slots: int, steps_per_sync: int, eos_at: Op
         for _ in range(steps_per_sync):
             ids = [tok(sch.slot_req[b], count[b] + 1) if sch.slot_req[b] is not None and row_pos[b] >= 0 else -7 for b in range(B)]
             slot_step_model(ids, row_pos, count, bud, history, cur, [0])
-        sch.after_chunk(steps_per_sync, row_pos, count, lambda b, m: [history[k][b] for k in range(m)], before)
+        sch.after_chunk(steps_per_sync, row_pos, count, lambda b, m: [history[k][b] for k in range(m)], before,
+                        (lambda b, m: extra(sch.slot_req[b], m)) if sch.logprobs is not None else None)
         boundary += 1
     return sch, log

@@ -167,14 +167,20 @@ def chat(model, image: Union[str, "Image.Image", torch.Tensor], text: str, histo
 
 
 @torch.inference_mode()
-def chat_many(model, items, generation_config=None, max_batch=64, share_prefix=False, generation_configs=None, seeds=None, prefix_cache=None):
+def chat_many(model, items, generation_config=None, max_batch=64, share_prefix=False, generation_configs=None, seeds=None, prefix_cache=None,
+              logprobs=None):
     """The bulk form of chat(): items = [(image, text) or (image, text, history), ...] -> [(response, history), ...].  Every prompt is built as
     chat() builds it, the queue is answered by model.generate_many (in-flight batching over max_batch slots) and every response is appended
     to its item's history exactly as chat() appends it.  share_prefix: generate_many's switch -- the system prompt every item begins with and the
     image slot of items about one image are computed once.  generation_configs / seeds: optional lists with one entry per item (None: the
     queue's config / the default generator), forwarded as generate_many's `generation_config` and `seed` request keys -- every item is then
     answered under its own config, and a seeded item draws the same uniforms whatever else is in the queue.  prefix_cache: generate_many's
-    (model.new_prefix_cache(), with share_prefix=True): the system prompt and the image slots survive the call."""
+    (model.new_prefix_cache(), with share_prefix=True): the system prompt and the image slots survive the call.
+    logprobs=k (generate_many's; None: nothing changes): -> [(response, history, output), ...] with output the item's
+    RequestOutput(tokens, logprobs, top_ids, top_logprobs) -- the log-probabilities of the RAW distribution, before any processor or
+    warper of the config, one row per generated token.  `target_ids` is not offered here."""
+    from .inflight import check_logprobs
+    logprobs = check_logprobs(logprobs)
     for name, lst in (("generation_configs", generation_configs), ("seeds", seeds)):
         if lst is not None and len(lst) != len(items):
             raise ValueError(f"chat_many: {name} has {len(lst)} entries for {len(items)} items")
@@ -197,12 +203,13 @@ def chat_many(model, items, generation_config=None, max_batch=64, share_prefix=F
         if seeds is not None and seeds[i] is not None:
             r["seed"] = seeds[i]
     outs = model.generate_many(requests, max_batch=max_batch, generation_config=gc, share_prefix=share_prefix,
-                               **({} if prefix_cache is None else dict(prefix_cache=prefix_cache)))
+                               **({} if prefix_cache is None else dict(prefix_cache=prefix_cache)),
+                               **({} if logprobs is None else dict(logprobs=logprobs)))
     results = []
-    for toks, history in zip(outs, histories):
-        response = model.tokenizer.decode(toks, skip_special_tokens=True)
+    for out, history in zip(outs, histories):
+        response = model.tokenizer.decode(out if logprobs is None else out.tokens, skip_special_tokens=True)
         history.append({"type": "response", "value": response})
-        results.append((response, history))
+        results.append((response, history) if logprobs is None else (response, history, out))
     return results
 
 

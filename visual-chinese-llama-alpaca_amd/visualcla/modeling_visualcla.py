@@ -1222,11 +1222,12 @@ class VisualCLAModel:
         if bad:
             raise ValueError("generate_many (in-flight batching) cannot be combined with " + ", ".join(bad))
 
-    def _inflight_request(self, i: int, r) -> dict:
-        """one entry of generate_many's `requests` -> ids [T] int64, pixel_values [C, H, W] or None, attention_mask [T] or None (on the device)"""
+    def _inflight_request(self, i: int, r, logprobs: Optional[int] = None) -> dict:
+        """one entry of generate_many's `requests` -> ids [T] int64, pixel_values [C, H, W] or None, attention_mask [T] or None (on the device);
+        `target` (a host list of ids, or None): the request's target_ids -- only with `logprobs`, never beside max_new_tokens"""
         if not isinstance(r, dict) or r.get("input_ids") is None:
             raise ValueError(f"request {i}: a dict with `input_ids` is required")
-        unknown = set(r) - {"input_ids", "pixel_values", "attention_mask", "max_new_tokens", "generation_config", "seed"}
+        unknown = set(r) - {"input_ids", "pixel_values", "attention_mask", "max_new_tokens", "generation_config", "seed", "target_ids"}
         if unknown:
             raise ValueError(f"request {i}: unknown keys {sorted(unknown)}")
 
@@ -1252,7 +1253,18 @@ class VisualCLAModel:
         seed = r.get("seed")
         if seed is not None and (isinstance(seed, bool) or not isinstance(seed, int)):
             raise ValueError(f"request {i}: seed must be an integer (got {seed!r})")
-        return dict(ids=ids, px=row(r.get("pixel_values"), 3, "pixel_values"), am=am, max_new_tokens=mnt, generation_config=rc, seed=seed)
+        target = None
+        if r.get("target_ids") is not None:
+            if logprobs is None:
+                raise ValueError(f"request {i}: target_ids needs generate_many(..., logprobs=k) (a scored continuation returns log-probabilities)")
+            if mnt is not None:
+                raise ValueError(f"request {i}: target_ids and max_new_tokens exclude each other (the budget of a forced request is len(target_ids))")
+            tg = torch.as_tensor(r["target_ids"])
+            if tg.dim() != 1 or tg.numel() < 1 or tg.dtype.is_floating_point or tg.dtype == torch.bool:
+                raise ValueError(f"request {i}: target_ids must be a 1-D sequence of at least one integer id (got shape {tuple(tg.shape)}, {tg.dtype})")
+            target = [int(x) for x in tg.tolist()]
+        return dict(ids=ids, px=row(r.get("pixel_values"), 3, "pixel_values"), am=am, max_new_tokens=mnt, generation_config=rc, seed=seed,
+                    target=target)
 
     def _request_configs(self, gc, reqs):
         """the resolved generation config of every request -> (configs, class of every request, one config per class).  A request without
@@ -1294,7 +1306,7 @@ class VisualCLAModel:
         def own_budget(rc) -> bool:                               # does the request's config state a budget of its own?
             get = rc.get if isinstance(rc, dict) else (lambda k: getattr(rc, k, None))
             return get("max_new_tokens") is not None or (get("max_length") is not None and get("max_length") != GenerationConfig().max_length)
-        return [int(r["max_new_tokens"]) if r["max_new_tokens"] is not None else
+        return [len(r["target"]) if r.get("target") is not None else int(r["max_new_tokens"]) if r["max_new_tokens"] is not None else
                 new_token_budget(g if (r["generation_config"] is not None and own_budget(r["generation_config"])) else gc, T)
                 for r, g, T in zip(reqs, gcs, lens)]
 
@@ -1333,7 +1345,8 @@ class VisualCLAModel:
 
     @torch.no_grad()
     def generate_many(self, requests, max_batch: int = 64, generation_config=None, steps_per_sync: int = 8, use_graph: Optional[bool] = None,
-                      share_prefix: bool = False, prefix_pool_tokens: Optional[int] = None, prefix_cache=None, **kwargs):
+                      share_prefix: bool = False, prefix_pool_tokens: Optional[int] = None, prefix_cache=None, logprobs: Optional[int] = None,
+                      **kwargs):
         """In-flight batching over a queue: -> List[LongTensor [n_i]] in request order, the NEW tokens of every request, its eos included
         and nothing behind it.  requests: dicts with `input_ids` ([T] or [1, T]), optional `pixel_values`, `attention_mask`, `max_new_tokens`
         (default: the config's budget by generate()'s rules for that prompt), `generation_config`, `seed`.
@@ -1366,9 +1379,22 @@ class VisualCLAModel:
         and reuses max(cached rows, planned rows) from one of the two sources; after every admission pass the full 16-row blocks of the
         admitted prompts are copied into the cache (visualcla/prefix_cache.py, csrc/kv_blocks.hip).  Same
         results, under the terms of share_prefix.  With a cache a queue of one request (or max_batch=1) also takes the slots route.
-        last_inflight_stats gains cache_rows_reused, cache_blocks_inserted, cache_evictions, cache_insert_skipped."""
-        from .inflight import InflightScheduler
+        last_inflight_stats gains cache_rows_reused, cache_blocks_inserted, cache_evictions, cache_insert_skipped.
+
+        logprobs=k (an int in 0..20; None: nothing changes): result[i] is a RequestOutput(tokens, logprobs, top_ids, top_logprobs)
+        (visualcla/inflight.py, csrc/logprobs.hip).  tokens: what is returned without the argument.  logprobs
+        float32 [n_i]: entry t is log_softmax(RAW logits of step t)[tokens[t]].  top_ids int64 / top_logprobs float32 [n_i, k]: the k
+        most likely tokens of that distribution, descending, ties by the lower id (so top_ids[:, 0] == tokens under plain greedy).  RAW:
+        the fp32 distribution the lm_head produced, BEFORE repetition penalty, n-gram bans, the min_new_tokens floor, temperature, top-k
+        or top-p -- it does not depend on the request's config (vLLM's default; processed scores are not offered).  The request key
+        `target_ids` (1-D ints, only with logprobs, not beside max_new_tokens) makes the request TEACHER-FORCED: at step t its slot takes
+        target_ids[t] instead of the selected id, its budget is len(target_ids), tokens == target_ids (cut behind the first eos of its
+        config), logprobs scores the targets and top_* still describes the model's own distribution at every position.  A forced request
+        draws no uniforms.  With logprobs a queue of one request (or max_batch=1) takes the slots route at one slot.
+        last_inflight_stats gains `logprobs` and `forced_requests`."""
+        from .inflight import InflightScheduler, RequestOutput, check_logprobs
         from .prefix_cache import PrefixCache
+        logprobs = check_logprobs(logprobs)                       # before anything else: the argument by name
         if prefix_cache is not None:
             if not share_prefix:
                 raise ValueError("generate_many: prefix_cache needs share_prefix=True (only the ragged admission of share_prefix places a request "
@@ -1378,7 +1404,14 @@ class VisualCLAModel:
         from .logits_processors import new_token_budget
         gc = self._resolve_generation_config(generation_config, kwargs)
         t = self.config.text_config
-        reqs = [self._inflight_request(i, r) for i, r in enumerate(requests)]
+        reqs = [self._inflight_request(i, r, logprobs) for i, r in enumerate(requests)]
+        targets = [r["target"] for r in reqs]
+        for i, tg in enumerate(targets):
+            if tg is not None and not all(0 <= x < t["vocab_size"] for x in tg):
+                raise ValueError(f"request {i}: target_ids outside the vocabulary 0..{t['vocab_size'] - 1}")
+        if logprobs and t["vocab_size"] > _lib.SAMPLE_MAX_VOCAB:
+            raise ValueError(f"generate_many: logprobs={logprobs} with vocab_size={t['vocab_size']} (the top-k pass holds a row of at most "
+                             f"{_lib.SAMPLE_MAX_VOCAB} logits in registers; logprobs=0 has no such limit)")
         per_request = any(r["generation_config"] is not None for r in reqs)
         gcs, cls, class_gcs = self._request_configs(gc, reqs) if per_request else ([gc] * len(reqs), [0] * len(reqs), [gc])
         seeds = [r["seed"] for r in reqs]
@@ -1401,16 +1434,19 @@ class VisualCLAModel:
             self._refuse_per_request_conflicts(class_gcs, [[i for i, c in enumerate(cls) if c == k] for k in range(len(class_gcs))],
                                                [min(b, t["max_position_embeddings"]) for b in budgets], t["vocab_size"],
                                                bool(getattr(self, "_kv_fp8", False)), bool(share_prefix), bool(self.image_at_head), masked)
-        extra_stats = dict(config_classes=len(class_gcs), sampler_rows=sum(self._uses_sampler(g) for g in gcs),
+        extra_stats = dict(config_classes=len(class_gcs), sampler_rows=sum(self._uses_sampler(g) for g, tg in zip(gcs, targets) if tg is None),
                            seeded=sum(sd is not None for sd in seeds))
+        if logprobs is not None:
+            extra_stats.update(logprobs=logprobs, forced_requests=sum(tg is not None for tg in targets))
         # raises for a prompt that leaves no room, by index, before any kernel runs
         sched = InflightScheduler(lens, budgets, [r["px"] is not None for r in reqs], max_batch, t["max_position_embeddings"], self.image_at_head,
-                                  steps_per_sync, share_prefix=bool(share_prefix))
+                                  steps_per_sync, share_prefix=bool(share_prefix), logprobs=logprobs, targets=targets)
         if use_graph is None:
             use_graph = os.environ.get("VCLA_DECODE_GRAPH", "1") != "0"
-        if sched.slots == 1 and (prefix_cache is None or not reqs):
+        if sched.slots == 1 and ((prefix_cache is None and logprobs is None) or not reqs):
             # max_batch = 1 or a single request: generate() per request (the persistent B = 1 step is the fast path there).  With a prefix
-            # cache such a queue stays on the slots route, at one slot: generate() has no place for cached rows
+            # cache such a queue stays on the slots route, at one slot: generate() has no place for cached rows; with logprobs too: the
+            # persistent B = 1 step folds its greedy tail and produces no logits
             out = []
             for i, r in enumerate(reqs):
                 self._request_seed = seeds[i]                     # the private hook _draw_uniforms reads: no public argument of generate()
@@ -1446,7 +1482,8 @@ class VisualCLAModel:
             side.wait_stream(cur_stream)
         with torch.cuda.device(self._device), torch.cuda.stream(side if side is not None else cur_stream):
             try:
-                out = self._inflight_on_stream(class_gcs[0], reqs, sched, bool(use_graph), plan, gcs if len(class_gcs) > 1 else None, seeds, pstate)
+                out = self._inflight_on_stream(class_gcs[0], reqs, sched, bool(use_graph), plan, gcs if len(class_gcs) > 1 else None, seeds, pstate,
+                                               logprobs)
             except BaseException:
                 if pstate is not None:                            # the index may name blocks whose copies were never enqueued
                     prefix_cache.end()
@@ -1456,6 +1493,11 @@ class VisualCLAModel:
         self.last_inflight_stats.update(extra_stats, **cache_stats)
         if side is not None:
             cur_stream.wait_stream(side)
+        if logprobs is not None:
+            dev = self._device
+            out = [RequestOutput(torch.tensor(o.tokens, dtype=torch.int64, device=dev), torch.tensor(o.logprobs, dtype=torch.float32, device=dev),
+                                 torch.tensor(o.top_ids, dtype=torch.int64, device=dev).view(len(o.tokens), logprobs),
+                                 torch.tensor(o.top_logprobs, dtype=torch.float32, device=dev).view(len(o.tokens), logprobs)) for o in out]
         return out
 
     def _prefix_plan(self, reqs, slots: int, pool_rows: Optional[int], keys=None, prompts=None):
@@ -1537,9 +1579,36 @@ class VisualCLAModel:
         if per["rows_dev"] is not None:
             per["rows_dev"][sl] = _lib.sample_row_bytes(_lib.sample_row_table([per["kw_of"][i] for i in requests]), len(requests)).to(self._device)
 
-    def _inflight_first(self, logits, requests, sl, samp_kw, uni, per, hist):
+    def _inflight_first(self, logits, requests, sl, samp_kw, uni, per, hist, lp=None):
         """the first token of the requests whose prefill produced `logits` (row j = requests[j], slot sl[j]): the same selector as the steps,
-        at history length 0 -- argmax, the uniform sampler, or the table entry with the admitted requests' own records"""
+        at history length 0 -- argmax, the uniform sampler, or the table entry with the admitted requests' own records.
+        lp (logprobs): the stats pass over the raw logits before the selector (a sampler then works on the copy), the pick with the
+        requests' forced[0] behind it; the values go to row 0 of the slots' columns and into lp["first"][request]."""
+        if lp is None:
+            return self._inflight_select(logits, requests, sl, samp_kw, uni, per, hist)
+        G, k = len(requests), lp["k"]
+        zeros = torch.zeros(G, dtype=torch.int32, device=self._device)
+        t_lp = torch.empty(1, G, dtype=torch.float32, device=self._device)
+        t_ids = torch.empty(1, G, k, dtype=torch.int64, device=self._device) if k else None
+        t_top = torch.empty(1, G, k, dtype=torch.float32, device=self._device) if k else None
+        f0 = lp["forced"][0, sl].view(1, G).contiguous() if lp["forced"] is not None else None
+        args = _lib.logprob_args(k, t_lp, t_ids, t_top, f0)
+        sampler = samp_kw is not None or (per is not None and per["rows_dev"] is not None)
+        work = torch.empty_like(logits) if sampler else None     # the sampler modifies its input; the gather needs the raw rows
+        lse = _lib.logprob_rows(logits, zeros, args, 1, copy=work)
+        first = self._inflight_select(work if sampler else logits, requests, sl, samp_kw, uni, per, hist)
+        _lib.logprob_pick(logits, zeros, args, 1, lse, first)
+        lp["lp"][0, sl] = t_lp[0]
+        if k:
+            lp["top_ids"][0, sl] = t_ids[0]
+            lp["top_lp"][0, sl] = t_top[0]
+        a, b_, c = t_lp[0].tolist(), (t_ids[0].tolist() if k else [[]] * G), (t_top[0].tolist() if k else [[]] * G)
+        for j, i in enumerate(requests):
+            lp["first"][i] = ([a[j]], [b_[j]], [c[j]])
+        return first
+
+    def _inflight_select(self, logits, requests, sl, samp_kw, uni, per, hist):
+        """the selector of _inflight_first (`logits` is modified by a sampler)"""
         G = len(requests)
         u0 = uni[0, sl].view(1, G).contiguous() if uni is not None else None
         if per is not None and per["rows_dev"] is not None:
@@ -1550,9 +1619,10 @@ class VisualCLAModel:
             return _lib.argmax(logits)
         return _lib.sample(logits, _lib.sample_args(uniforms=u0, **samp_kw), n_hist=0)
 
-    def _inflight_on_stream(self, gc, reqs, sched, use_graph: bool, plan=None, gcs=None, seeds=None, pstate=None):
+    def _inflight_on_stream(self, gc, reqs, sched, use_graph: bool, plan=None, gcs=None, seeds=None, pstate=None, logprobs=None):
         """gcs None: one config `gc` for the whole queue.  Else gcs[i] is request i's config, there are at least two distinct ones, and the
-        step reads per-slot tables (_per_request_tables).  pstate: the call's state of a prefix cache (PrefixCache.begin), or None."""
+        step reads per-slot tables (_per_request_tables).  pstate: the call's state of a prefix cache (PrefixCache.begin), or None.
+        logprobs (k or None): the step also runs the stats pass and the pick (csrc/logprobs.hip); sched.targets[i] forces request i."""
         import time
         from .logits_processors import min_token_floor
         lib = _lib.load()
@@ -1571,6 +1641,7 @@ class VisualCLAModel:
             if samp_kw is None:
                 raise ValueError("generate_many: the generation config does not map onto the device sampler")
         draws = [bool(gc.do_sample)] * sched.n if per is None else per["do_sample"]
+        draws = [d and tg is None for d, tg in zip(draws, sched.targets)]     # a forced request draws no uniforms
         # ---- the slot table: one int32 vector (row_pos | count | hist_len | budget | summary) so that a boundary is ONE copy to the host
         W = _lib.SLOT_SUMMARY_WORDS
         st = self._typed_buf("if_state", (4 * B + W,), torch.int32)
@@ -1584,7 +1655,19 @@ class VisualCLAModel:
         kv = self._typed_buf("if_kv", (t["num_hidden_layers"], 2, B, H, ctx_max, d), self._dtype)
         km = self._typed_buf("if_km", (B, ctx_max), torch.int32)
         km.fill_(1)
-        ws = self._buf("slots", lib.vcla_llama_workspace_bytes(self._ctx, B, 1))
+        lp = lpa = None
+        ws_bytes = lib.vcla_llama_workspace_bytes(self._ctx, B, 1)
+        if logprobs is not None:
+            k = int(logprobs)
+            ws_bytes += lib.vcla_logprob_scratch_bytes(B, t["vocab_size"], int(samp_kw is not None))
+            lp = dict(k=k, lp=self._typed_buf("if_lp", (cap, B), torch.float32),
+                      top_ids=self._typed_buf("if_top_ids", (cap, B, k), torch.int64) if k else None,
+                      top_lp=self._typed_buf("if_top_lp", (cap, B, k), torch.float32) if k else None,
+                      forced=self._typed_buf("if_forced", (cap, B), torch.int64) if any(tg is not None for tg in sched.targets) else None, first={})
+            if lp["forced"] is not None:
+                lp["forced"].fill_(-1)
+            lpa = _lib.logprob_args(k, lp["lp"], lp["top_ids"], lp["top_lp"], lp["forced"])
+        ws = self._buf("slots", ws_bytes)
         slots = _lib.slot_args(eos, row_pos, count, budget, hist_len, hist, cur, summary)
         samp = _lib.sample_args(uniforms=uni, history=hist, **samp_kw) if samp_kw is not None else None
         count_h = [0] * B
@@ -1612,19 +1695,30 @@ class VisualCLAModel:
                         else:                                   # a function of (seed, budget) alone, whatever else is in the queue
                             uni[:sched.budget[i], b] = torch.rand(sched.budget[i], device=dev,
                                                                   generator=torch.Generator(device=dev).manual_seed(int(seeds[i])))
+                if lp is not None and lp["forced"] is not None:   # the forced column of every slot that is filled: -1 = free-running
+                    for g in groups:
+                        for i, b in zip(g.requests, g.slots):
+                            lp["forced"][:, b] = -1
+                            if sched.targets[i] is not None:
+                                lp["forced"][:sched.budget[i], b] = torch.tensor(sched.targets[i], dtype=torch.int64, device=dev)
                 for g in groups:
                     if per is not None:
                         self._inflight_fill_rows(per, g.requests, g.slots)
                     if g.ragged:
-                        self._inflight_admit_ragged(g, reqs, sched, eos, samp_kw, uni, kv, km, st, hist, cur, count_h, share, per)
+                        self._inflight_admit_ragged(g, reqs, sched, eos, samp_kw, uni, kv, km, st, hist, cur, count_h, share, per, lp)
                     else:
-                        self._inflight_admit(g, reqs, sched, eos, samp_kw, uni, kv, km, st, hist, cur, count_h, per)
+                        self._inflight_admit(g, reqs, sched, eos, samp_kw, uni, kv, km, st, hist, cur, count_h, per, lp)
             t1 = time.perf_counter()
             t_adm += t1 - t0
             if sched.finished:
                 break
             n = sched.steps_per_sync
-            if per is None:
+            if lp is not None:
+                _lib.check(lib.vcla_llama_decode_slots_logprobs(self._ctx, C.byref(slots), n, kv.data_ptr(), ctx_max, km.data_ptr(), ws.data_ptr(),
+                                                                ws.numel(), int(use_graph), C.byref(samp) if samp is not None else None,
+                                                                per["eos_dev"].data_ptr() if per is not None else None,
+                                                                _lib.ptr(per["rows_dev"]) if per is not None else None, C.byref(lpa), _lib.stream_ptr()))
+            elif per is None:
                 _lib.check(lib.vcla_llama_decode_slots(self._ctx, C.byref(slots), n, kv.data_ptr(), ctx_max, km.data_ptr(), ws.data_ptr(), ws.numel(),
                                                        int(use_graph), C.byref(samp) if samp is not None else None, _lib.stream_ptr()))
             else:
@@ -1634,9 +1728,19 @@ class VisualCLAModel:
             host = st.tolist()                                  # the one synchronisation of the boundary: positions, counts, n_active
             pos_h, cnt_h = host[:B], host[B:2 * B]
             done = [b for b in range(B) if sched.slot_req[b] is not None and pos_h[b] < 0]
-            cols = hist[:, torch.tensor(done, device=dev)].t().tolist() if done else []
+            di = torch.tensor(done, device=dev) if done else None
+            cols = hist[:, di].t().tolist() if done else []
             where = {b: k for k, b in enumerate(done)}
-            sched.after_chunk(n, pos_h, cnt_h, lambda b, m: cols[where[b]][:m], count_h)
+            extras_of = None
+            if lp is not None:                                  # the finished slots' columns of the logprob buffers, in the same indexed copy
+                lcols = lp["lp"][:, di].t().tolist() if done else []
+                icols = lp["top_ids"][:, di].permute(1, 0, 2).tolist() if done and lp["k"] else None
+                tcols = lp["top_lp"][:, di].permute(1, 0, 2).tolist() if done and lp["k"] else None
+
+                def extras_of(b, m):
+                    w = where[b]
+                    return lcols[w][:m], (icols[w][:m] if icols is not None else [[]] * m), (tcols[w][:m] if tcols is not None else [[]] * m)
+            sched.after_chunk(n, pos_h, cnt_h, lambda b, m: cols[where[b]][:m], count_h, extras_of)
             count_h = cnt_h
             t_steps += time.perf_counter() - t1
         # beside the counters: host seconds spent in admission / in steps, and the position every request's slot decoded from (its group's longest prompt)
@@ -1646,9 +1750,11 @@ class VisualCLAModel:
                                             pool_entries=len(plan.entries), pool_bytes=share["pool"].numel() * share["pool"].element_size(),
                                             pool_rows=int(share["pool"].shape[0]), admission_passes=share["passes"], rows_calls=share["calls"],
                                             workspace_bytes=int(self._ws["extend_rows"].numel()) if "extend_rows" in self._ws else 0)
+        if lp is not None:
+            return sched.ordered_results()                      # RequestOutput tuples of lists: generate_many makes the tensors
         return [torch.tensor(toks, dtype=torch.int64, device=dev) for toks in sched.ordered_results()]
 
-    def _inflight_admit(self, g, reqs, sched, eos, samp_kw, uni, kv, km, st, hist, cur, count_h, per=None) -> None:
+    def _inflight_admit(self, g, reqs, sched, eos, samp_kw, uni, kv, km, st, hist, cur, count_h, per=None, lp=None) -> None:
         """One admission group through the request path of generate() as a left-padded batch (checks, vision stack, embedding splice, prefill
         into a private cache), then into its slots: K/V rows [0, T_group), the pad holes of the key mask, the first token, the slot state."""
         dev = self._device
@@ -1680,12 +1786,12 @@ class VisualCLAModel:
         km[sl] = 1
         if am2 is not None:
             km[sl, :Tg] = am2.to(torch.int32)
-        first = self._inflight_first(logits, g.requests, sl, samp_kw, uni, per, hist)
+        first = self._inflight_first(logits, g.requests, sl, samp_kw, uni, per, hist, lp)
         first_h = first.tolist()                                # synchronises
         live = []
         for j, (i, b) in enumerate(zip(g.requests, g.slots)):
             ended = first_h[j] in (eos if per is None else per["eos_of"][i]) or sched.budget[i] == 1
-            sched.started(b, first_h[j], ended)
+            sched.started(b, first_h[j], ended, lp["first"].pop(i) if lp is not None else None)
             if not ended:
                 live.append((b, first_h[j], sched.budget[i]))
         if live:
@@ -1702,7 +1808,7 @@ class VisualCLAModel:
 
     RAGGED_MAX_ROWS = 8192      # packed rows of one vcla_llama_extend_rows call (its workspace is sized for them); longer passes are cut
 
-    def _inflight_admit_ragged(self, g, reqs, sched, eos, samp_kw, uni, kv, km, st, hist, cur, count_h, share, per=None) -> None:
+    def _inflight_admit_ragged(self, g, reqs, sched, eos, samp_kw, uni, kv, km, st, hist, cur, count_h, share, per=None, lp=None) -> None:
         """share_prefix=True: the requests admitted at one boundary, every one at position 0 of its slot.  In the passes of prefix.passes: copy
         the rows [0, P_i) each request reuses from the pool into its slot (one indexed copy per pass), run the vision stack over the images
         that are needed, then ONE vcla_llama_extend_rows over the rows [P_i, T_i) of all of them, written straight into the slots; the
@@ -1769,7 +1875,7 @@ class VisualCLAModel:
                     self._inflight_logits_tap.append((list(call), logits.detach().clone()))
                 sl = torch.tensor([slot_of[i] for i in call], device=dev)
                 km[sl] = 1
-                first = self._inflight_first(logits, call, sl, samp_kw, uni, per, hist)
+                first = self._inflight_first(logits, call, sl, samp_kw, uni, per, hist, lp)
                 for i, tok in zip(call, first.tolist()):          # synchronises
                     first_of[i] = tok
             share["reused"] += sum(P[i] for i in members)
@@ -1793,7 +1899,7 @@ class VisualCLAModel:
         live = []
         for i, b in zip(g.requests, g.slots):
             ended = first_of[i] in (eos if per is None else per["eos_of"][i]) or sched.budget[i] == 1
-            sched.started(b, first_of[i], ended)
+            sched.started(b, first_of[i], ended, lp["first"].pop(i) if lp is not None else None)
             if not ended:
                 live.append((b, first_of[i], sched.budget[i], plan.T[i]))
         if live:
