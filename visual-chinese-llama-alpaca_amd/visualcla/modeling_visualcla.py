@@ -17,7 +17,7 @@ from typing import Dict, List, Optional, Union
 
 import torch
 
-from . import _lib
+from . import _lib, slots_run
 from .configuration_visualcla import VisualCLAConfig
 from .weights import add_fp8_copies, extend_position_embedding, fold_lora, pack_state_dict, random_packed, unpack_state_dict  # noqa: F401
 
@@ -1468,10 +1468,10 @@ class VisualCLAModel:
             return out
         plan = pstate = None
         if share_prefix and prefix_cache is None:
-            plan = self._prefix_plan(reqs, sched.slots, prefix_pool_tokens)
+            plan = slots_run._prefix_plan(self, reqs, sched.slots, prefix_pool_tokens)
         elif share_prefix:                                        # the plan exactly as without a cache, then one lookup per request
-            keys, prompts = self._image_keys(reqs), self._prompt_lists(reqs)
-            plan = self._prefix_plan(reqs, sched.slots, prefix_pool_tokens, keys, prompts)
+            keys, prompts = slots_run._image_keys(self, reqs), slots_run._prompt_lists(reqs)
+            plan = slots_run._prefix_plan(self, reqs, sched.slots, prefix_pool_tokens, keys, prompts)
             pstate = prefix_cache.begin(reqs, plan, keys, prompts, self._special_ids()[2] if any(k is not None for k in keys) else None)
         cur_stream = torch.cuda.current_stream(self._device)
         side = None
@@ -1482,8 +1482,7 @@ class VisualCLAModel:
             side.wait_stream(cur_stream)
         with torch.cuda.device(self._device), torch.cuda.stream(side if side is not None else cur_stream):
             try:
-                out = self._inflight_on_stream(class_gcs[0], reqs, sched, bool(use_graph), plan, gcs if len(class_gcs) > 1 else None, seeds, pstate,
-                                               logprobs)
+                out = slots_run.SlotsRun(self, class_gcs[0], reqs, sched, bool(use_graph), plan, gcs if len(class_gcs) > 1 else None, seeds, pstate, logprobs).run()
             except BaseException:
                 if pstate is not None:                            # the index may name blocks whose copies were never enqueued
                     prefix_cache.end()
@@ -1499,417 +1498,3 @@ class VisualCLAModel:
                                  torch.tensor(o.top_ids, dtype=torch.int64, device=dev).view(len(o.tokens), logprobs),
                                  torch.tensor(o.top_logprobs, dtype=torch.float32, device=dev).view(len(o.tokens), logprobs)) for o in out]
         return out
-
-    def _prefix_plan(self, reqs, slots: int, pool_rows: Optional[int], keys=None, prompts=None):
-        """the prefix plan of a queue (visualcla/prefix.py) from its ids and images (keys / prompts: _image_keys / _prompt_lists of the
-        queue, when the caller needs them too)"""
-        from . import prefix
-        if pool_rows is not None and int(pool_rows) < 0:
-            raise ValueError(f"prefix_pool_tokens must be >= 0 (got {pool_rows})")
-        keys = self._image_keys(reqs) if keys is None else keys
-        prompts = self._prompt_lists(reqs) if prompts is None else prompts
-        return prefix.plan(prompts, keys, self._special_ids()[2] if any(k is not None for k in keys) else None, slots, pool_rows)
-
-    @staticmethod
-    def _prompt_lists(reqs):
-        """the ids of every request as host lists (one copy back when the prompts have one length)"""
-        return [r["ids"].tolist() for r in reqs] if len({int(r["ids"].numel()) for r in reqs}) != 1 else torch.stack([r["ids"] for r in reqs]).tolist()
-
-    def _image_keys(self, reqs):
-        """one key per request, None without an image, equal for equal images: the index of the first request that carries the image.
-        Images are compared BY VALUE, as the vision stack sees them (model dtype), inside this pass: one fingerprint per image (a launch
-        over the stacked images, one copy back) buckets them, one row-wise comparison of every image with the first of its bucket
-        confirms (a second copy back); the same tensor object needs neither."""
-        keys: List[Optional[int]] = [None] * len(reqs)
-        with_px = [i for i, r in enumerate(reqs) if r["px"] is not None]
-        by_obj: Dict[int, int] = {}
-        firsts = []                                               # the first request of every distinct tensor object
-        for i in with_px:
-            if by_obj.setdefault(id(reqs[i]["px"]), i) == i:
-                firsts.append(i)
-        by_shape: Dict[tuple, List[int]] = {}
-        for i in firsts:
-            by_shape.setdefault(tuple(reqs[i]["px"].shape), []).append(i)
-        for members in by_shape.values():
-            flat = torch.stack([reqs[i]["px"].to(self._dtype) for i in members]).flatten(1)
-            w = torch.linspace(1.0, 2.0, flat.shape[1], device=flat.device, dtype=torch.float32)
-            prints = torch.stack([flat.float().sum(1), (flat.float() * w).sum(1)], dim=1).tolist()
-            rep_of: Dict[tuple, int] = {}
-            cand = [rep_of.setdefault(tuple(fp), k) for k, fp in enumerate(prints)]
-            same = (flat == flat[torch.tensor(cand, device=flat.device)]).all(dim=1).tolist()
-            for k, i in enumerate(members):
-                keys[i] = members[cand[k]] if same[k] else i      # (a fingerprint collision of different images: a key of its own)
-        for i in with_px:
-            keys[i] = keys[by_obj[id(reqs[i]["px"])]]
-        return keys
-
-    def _per_request_tables(self, gcs, sched):
-        """Requests under different configs: what the slots loop needs beside the queue-wide state.  eos_of[i] /
-        kw_of[i]: request i's eos list and its vcla_sample_row fields; eos_dev int32 [B, SLOT_MAX_EOS] and rows_dev uint8 [B, 64]: the
-        per-slot tables in device memory the captured step reads (rows_dev None: no request needs the sampler, the step is argmax + the
-        per-row eos lookup).  A greedy request is a record with top_k = 1 and the greedy flag."""
-        B = sched.slots
-        eos_of = [self._eos_list(g) for g in gcs]
-        kw_by_cfg: Dict[int, Optional[dict]] = {}
-        table = any(self._uses_sampler(g) for g in gcs)
-        kw_of = []
-        for i, g in enumerate(gcs):
-            if id(g) not in kw_by_cfg:
-                kw = None
-                if self._uses_sampler(g):
-                    kw = self._device_sampling(g, max(sched.budget[j] for j, h in enumerate(gcs) if h is g), 0)
-                    if kw is None:
-                        raise ValueError(f"generate_many: the generation config of request {i} does not map onto the device sampler")
-                kw_by_cfg[id(g)] = dict(kw or {}, greedy=not g.do_sample)
-            kw_of.append(kw_by_cfg[id(g)])
-        if table:
-            _lib.sample_row_table(kw_of)                          # range checks of every record, before any kernel runs
-        eos_dev = self._typed_buf("if_eos_rows", (B, _lib.SLOT_MAX_EOS), torch.int32)
-        eos_dev.fill_(-1)
-        rows_dev = None
-        if table:
-            rows_dev = self._typed_buf("if_sample_rows", (B, C.sizeof(_lib.SampleRow)), torch.uint8)
-            rows_dev.copy_(_lib.sample_row_bytes(_lib.sample_row_table([dict(greedy=True)] * B)))
-        return dict(eos_of=eos_of, kw_of=kw_of, eos_dev=eos_dev, rows_dev=rows_dev, do_sample=[bool(g.do_sample) for g in gcs])
-
-    def _inflight_fill_rows(self, per, requests, slots) -> None:
-        """admission: the table rows of the slots it fills, rewritten between two chunks of steps"""
-        sl = torch.tensor(list(slots), device=self._device)
-        per["eos_dev"][sl] = _lib.slot_eos_rows([per["eos_of"][i] for i in requests]).to(self._device)
-        if per["rows_dev"] is not None:
-            per["rows_dev"][sl] = _lib.sample_row_bytes(_lib.sample_row_table([per["kw_of"][i] for i in requests]), len(requests)).to(self._device)
-
-    def _inflight_first(self, logits, requests, sl, samp_kw, uni, per, hist, lp=None):
-        """the first token of the requests whose prefill produced `logits` (row j = requests[j], slot sl[j]): the same selector as the steps,
-        at history length 0 -- argmax, the uniform sampler, or the table entry with the admitted requests' own records.
-        lp (logprobs): the stats pass over the raw logits before the selector (a sampler then works on the copy), the pick with the
-        requests' forced[0] behind it; the values go to row 0 of the slots' columns and into lp["first"][request]."""
-        if lp is None:
-            return self._inflight_select(logits, requests, sl, samp_kw, uni, per, hist)
-        G, k = len(requests), lp["k"]
-        zeros = torch.zeros(G, dtype=torch.int32, device=self._device)
-        t_lp = torch.empty(1, G, dtype=torch.float32, device=self._device)
-        t_ids = torch.empty(1, G, k, dtype=torch.int64, device=self._device) if k else None
-        t_top = torch.empty(1, G, k, dtype=torch.float32, device=self._device) if k else None
-        f0 = lp["forced"][0, sl].view(1, G).contiguous() if lp["forced"] is not None else None
-        args = _lib.logprob_args(k, t_lp, t_ids, t_top, f0)
-        sampler = samp_kw is not None or (per is not None and per["rows_dev"] is not None)
-        work = torch.empty_like(logits) if sampler else None     # the sampler modifies its input; the gather needs the raw rows
-        lse = _lib.logprob_rows(logits, zeros, args, 1, copy=work)
-        first = self._inflight_select(work if sampler else logits, requests, sl, samp_kw, uni, per, hist)
-        _lib.logprob_pick(logits, zeros, args, 1, lse, first)
-        lp["lp"][0, sl] = t_lp[0]
-        if k:
-            lp["top_ids"][0, sl] = t_ids[0]
-            lp["top_lp"][0, sl] = t_top[0]
-        a, b_, c = t_lp[0].tolist(), (t_ids[0].tolist() if k else [[]] * G), (t_top[0].tolist() if k else [[]] * G)
-        for j, i in enumerate(requests):
-            lp["first"][i] = ([a[j]], [b_[j]], [c[j]])
-        return first
-
-    def _inflight_select(self, logits, requests, sl, samp_kw, uni, per, hist):
-        """the selector of _inflight_first (`logits` is modified by a sampler)"""
-        G = len(requests)
-        u0 = uni[0, sl].view(1, G).contiguous() if uni is not None else None
-        if per is not None and per["rows_dev"] is not None:
-            rows = _lib.sample_row_bytes(_lib.sample_row_table([per["kw_of"][i] for i in requests]), G).to(self._device)
-            return _lib.sample_rows_table(logits, torch.zeros(G, dtype=torch.int32, device=self._device),
-                                          _lib.sample_args(uniforms=u0, history=hist), rows)
-        if samp_kw is None:
-            return _lib.argmax(logits)
-        return _lib.sample(logits, _lib.sample_args(uniforms=u0, **samp_kw), n_hist=0)
-
-    def _inflight_on_stream(self, gc, reqs, sched, use_graph: bool, plan=None, gcs=None, seeds=None, pstate=None, logprobs=None):
-        """gcs None: one config `gc` for the whole queue.  Else gcs[i] is request i's config, there are at least two distinct ones, and the
-        step reads per-slot tables (_per_request_tables).  pstate: the call's state of a prefix cache (PrefixCache.begin), or None.
-        logprobs (k or None): the step also runs the stats pass and the pick (csrc/logprobs.hip); sched.targets[i] forces request i."""
-        import time
-        from .logits_processors import min_token_floor
-        lib = _lib.load()
-        dev = self._device
-        t = self.config.text_config
-        B, ctx_max, cap = sched.slots, sched.ctx_max, sched.cap
-        seeds = seeds if seeds is not None else [None] * sched.n
-        per = self._per_request_tables(gcs, sched) if gcs is not None else None
-        eos = self._eos_list(gc) if per is None else []
-        rp = gc.repetition_penalty if gc.repetition_penalty is not None else 1.0
-        samp_kw = None
-        if per is not None:
-            samp_kw = {} if per["rows_dev"] is not None else None   # the scalar fields of the shared block are ignored by the table entry
-        elif gc.do_sample or rp != 1.0 or gc.no_repeat_ngram_size or (eos and min_token_floor(gc, 0) > 0):
-            samp_kw = self._device_sampling(gc, cap, 0)
-            if samp_kw is None:
-                raise ValueError("generate_many: the generation config does not map onto the device sampler")
-        draws = [bool(gc.do_sample)] * sched.n if per is None else per["do_sample"]
-        draws = [d and tg is None for d, tg in zip(draws, sched.targets)]     # a forced request draws no uniforms
-        # ---- the slot table: one int32 vector (row_pos | count | hist_len | budget | summary) so that a boundary is ONE copy to the host
-        W = _lib.SLOT_SUMMARY_WORDS
-        st = self._typed_buf("if_state", (4 * B + W,), torch.int32)
-        st.copy_(torch.tensor([-1] * B + [0] * B + [-1] * B + [0] * B + [0] * W, dtype=torch.int32))
-        row_pos, count, hist_len, budget, summary = st[:B], st[B:2 * B], st[2 * B:3 * B], st[3 * B:4 * B], st[4 * B:]
-        hist = self._typed_buf("if_hist", (cap, B), torch.int64)
-        cur = self._typed_buf("if_cur", (B,), torch.int64)
-        cur.zero_()
-        uni = self._typed_buf("if_uni", (cap, B), torch.float32) if any(draws) and samp_kw is not None else None
-        H, d = t["num_attention_heads"], t["hidden_size"] // t["num_attention_heads"]
-        kv = self._typed_buf("if_kv", (t["num_hidden_layers"], 2, B, H, ctx_max, d), self._dtype)
-        km = self._typed_buf("if_km", (B, ctx_max), torch.int32)
-        km.fill_(1)
-        lp = lpa = None
-        ws_bytes = lib.vcla_llama_workspace_bytes(self._ctx, B, 1)
-        if logprobs is not None:
-            k = int(logprobs)
-            ws_bytes += lib.vcla_logprob_scratch_bytes(B, t["vocab_size"], int(samp_kw is not None))
-            lp = dict(k=k, lp=self._typed_buf("if_lp", (cap, B), torch.float32),
-                      top_ids=self._typed_buf("if_top_ids", (cap, B, k), torch.int64) if k else None,
-                      top_lp=self._typed_buf("if_top_lp", (cap, B, k), torch.float32) if k else None,
-                      forced=self._typed_buf("if_forced", (cap, B), torch.int64) if any(tg is not None for tg in sched.targets) else None, first={})
-            if lp["forced"] is not None:
-                lp["forced"].fill_(-1)
-            lpa = _lib.logprob_args(k, lp["lp"], lp["top_ids"], lp["top_lp"], lp["forced"])
-        ws = self._buf("slots", ws_bytes)
-        slots = _lib.slot_args(eos, row_pos, count, budget, hist_len, hist, cur, summary)
-        samp = _lib.sample_args(uniforms=uni, history=hist, **samp_kw) if samp_kw is not None else None
-        count_h = [0] * B
-        t_adm = t_steps = 0.0
-        share = None
-        if plan is not None:                                    # the prefix pool of this call: [rows, L, 2, H, d], 2 L H d elements per row
-            n_rows = min(plan.pool_rows, plan.peak_pool_rows)
-            pool = torch.empty(n_rows, t["num_hidden_layers"], 2, H, d, dtype=self._dtype, device=dev)
-            share = dict(plan=plan, pool=pool, free=list(range(n_rows - 1, -1, -1)), rows={}, reused=0, computed=0, vision=0, passes=0, calls=0,
-                         P=plan.P, vis=plan.vision_needed, pstate=pstate)
-            if pstate is not None:                              # rows and vision runs as the cache and the plan combine (prefix_cache.combine)
-                share.update(P=pstate["P"], vis=pstate["vision"])
-        while not sched.finished:
-            t0 = time.perf_counter()
-            while True:                                         # a request whose first token ends it frees its slot within the boundary
-                groups = sched.admit(sched.free_slots())
-                if not groups:
-                    break
-                if uni is not None:                             # request i's own column of uniforms, drawn in request order
-                    for i, b in sorted((i, b) for g in groups for i, b in zip(g.requests, g.slots)):
-                        if not draws[i]:
-                            continue                            # a greedy row of the table draws at 0
-                        if seeds[i] is None:
-                            uni[:sched.budget[i], b] = torch.rand(sched.budget[i], device=dev)
-                        else:                                   # a function of (seed, budget) alone, whatever else is in the queue
-                            uni[:sched.budget[i], b] = torch.rand(sched.budget[i], device=dev,
-                                                                  generator=torch.Generator(device=dev).manual_seed(int(seeds[i])))
-                if lp is not None and lp["forced"] is not None:   # the forced column of every slot that is filled: -1 = free-running
-                    for g in groups:
-                        for i, b in zip(g.requests, g.slots):
-                            lp["forced"][:, b] = -1
-                            if sched.targets[i] is not None:
-                                lp["forced"][:sched.budget[i], b] = torch.tensor(sched.targets[i], dtype=torch.int64, device=dev)
-                for g in groups:
-                    if per is not None:
-                        self._inflight_fill_rows(per, g.requests, g.slots)
-                    if g.ragged:
-                        self._inflight_admit_ragged(g, reqs, sched, eos, samp_kw, uni, kv, km, st, hist, cur, count_h, share, per, lp)
-                    else:
-                        self._inflight_admit(g, reqs, sched, eos, samp_kw, uni, kv, km, st, hist, cur, count_h, per, lp)
-            t1 = time.perf_counter()
-            t_adm += t1 - t0
-            if sched.finished:
-                break
-            n = sched.steps_per_sync
-            if lp is not None:
-                _lib.check(lib.vcla_llama_decode_slots_logprobs(self._ctx, C.byref(slots), n, kv.data_ptr(), ctx_max, km.data_ptr(), ws.data_ptr(),
-                                                                ws.numel(), int(use_graph), C.byref(samp) if samp is not None else None,
-                                                                per["eos_dev"].data_ptr() if per is not None else None,
-                                                                _lib.ptr(per["rows_dev"]) if per is not None else None, C.byref(lpa), _lib.stream_ptr()))
-            elif per is None:
-                _lib.check(lib.vcla_llama_decode_slots(self._ctx, C.byref(slots), n, kv.data_ptr(), ctx_max, km.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                       int(use_graph), C.byref(samp) if samp is not None else None, _lib.stream_ptr()))
-            else:
-                _lib.check(lib.vcla_llama_decode_slots_rows(self._ctx, C.byref(slots), n, kv.data_ptr(), ctx_max, km.data_ptr(), ws.data_ptr(),
-                                                            ws.numel(), int(use_graph), C.byref(samp) if samp is not None else None,
-                                                            per["eos_dev"].data_ptr(), _lib.ptr(per["rows_dev"]), _lib.stream_ptr()))
-            host = st.tolist()                                  # the one synchronisation of the boundary: positions, counts, n_active
-            pos_h, cnt_h = host[:B], host[B:2 * B]
-            done = [b for b in range(B) if sched.slot_req[b] is not None and pos_h[b] < 0]
-            di = torch.tensor(done, device=dev) if done else None
-            cols = hist[:, di].t().tolist() if done else []
-            where = {b: k for k, b in enumerate(done)}
-            extras_of = None
-            if lp is not None:                                  # the finished slots' columns of the logprob buffers, in the same indexed copy
-                lcols = lp["lp"][:, di].t().tolist() if done else []
-                icols = lp["top_ids"][:, di].permute(1, 0, 2).tolist() if done and lp["k"] else None
-                tcols = lp["top_lp"][:, di].permute(1, 0, 2).tolist() if done and lp["k"] else None
-
-                def extras_of(b, m):
-                    w = where[b]
-                    return lcols[w][:m], (icols[w][:m] if icols is not None else [[]] * m), (tcols[w][:m] if tcols is not None else [[]] * m)
-            sched.after_chunk(n, pos_h, cnt_h, lambda b, m: cols[where[b]][:m], count_h, extras_of)
-            count_h = cnt_h
-            t_steps += time.perf_counter() - t1
-        # beside the counters: host seconds spent in admission / in steps, and the position every request's slot decoded from (its group's longest prompt)
-        self.last_inflight_stats = dict(sched.stats, admission_s=t_adm, steps_s=t_steps, ctx_max=ctx_max, decode_from=[sched.decode_from[i] for i in range(sched.n)])
-        if share is not None:
-            self.last_inflight_stats.update(rows_reused=share["reused"], rows_computed=share["computed"], vision_runs=share["vision"],
-                                            pool_entries=len(plan.entries), pool_bytes=share["pool"].numel() * share["pool"].element_size(),
-                                            pool_rows=int(share["pool"].shape[0]), admission_passes=share["passes"], rows_calls=share["calls"],
-                                            workspace_bytes=int(self._ws["extend_rows"].numel()) if "extend_rows" in self._ws else 0)
-        if lp is not None:
-            return sched.ordered_results()                      # RequestOutput tuples of lists: generate_many makes the tensors
-        return [torch.tensor(toks, dtype=torch.int64, device=dev) for toks in sched.ordered_results()]
-
-    def _inflight_admit(self, g, reqs, sched, eos, samp_kw, uni, kv, km, st, hist, cur, count_h, per=None, lp=None) -> None:
-        """One admission group through the request path of generate() as a left-padded batch (checks, vision stack, embedding splice, prefill
-        into a private cache), then into its slots: K/V rows [0, T_group), the pad holes of the key mask, the first token, the slot state."""
-        dev = self._device
-        B = sched.slots
-        rs = [reqs[i] for i in g.requests]
-        G = len(rs)
-        Tt = max(int(r["ids"].numel()) for r in rs)
-        ids = torch.zeros(G, Tt, dtype=torch.int64, device=dev)
-        am = torch.zeros(G, Tt, dtype=torch.int64, device=dev)
-        for j, r in enumerate(rs):
-            n = int(r["ids"].numel())
-            ids[j, Tt - n:] = r["ids"]
-            am[j, Tt - n:] = 1 if r["am"] is None else r["am"].to(torch.int64)
-        masked = any(r["am"] is not None or int(r["ids"].numel()) < Tt for r in rs)
-        px = torch.stack([r["px"] for r in rs]) if g.image else None
-        Q = self.config.visual_resampler_config["num_query_tokens"] if g.image else 0
-        img_pos, am2 = self._check_request(ids, am if masked else None, Q, for_generate=True)
-        img = self.embed_images(px) if px is not None else None
-        embeds, _ = self._embed(ids, img, img_pos)
-        Tg = embeds.shape[1]
-        if Tg != g.T:
-            raise ValueError(f"generate_many: group of requests {g.requests} embeds to {Tg} positions, the scheduler planned {g.T}")
-        own = self._new_cache(G, Tg)
-        logits = self._prefill(embeds, own, self._key_mask(am2, G, Tg, Tg), all_logits=False)
-        if self._inflight_logits_tap is not None:
-            self._inflight_logits_tap.append((list(g.requests), logits.detach().clone()))
-        sl = torch.tensor(g.slots, device=dev)
-        kv[:, :, sl, :, :Tg, :] = own.kv
-        km[sl] = 1
-        if am2 is not None:
-            km[sl, :Tg] = am2.to(torch.int32)
-        first = self._inflight_first(logits, g.requests, sl, samp_kw, uni, per, hist, lp)
-        first_h = first.tolist()                                # synchronises
-        live = []
-        for j, (i, b) in enumerate(zip(g.requests, g.slots)):
-            ended = first_h[j] in (eos if per is None else per["eos_of"][i]) or sched.budget[i] == 1
-            sched.started(b, first_h[j], ended, lp["first"].pop(i) if lp is not None else None)
-            if not ended:
-                live.append((b, first_h[j], sched.budget[i]))
-        if live:
-            lb = torch.tensor([x[0] for x in live], device=dev)
-            fi = torch.tensor([x[1] for x in live], dtype=torch.int64, device=dev)
-            st[lb] = Tg                                         # row_pos
-            st[B + lb] = 1                                      # count
-            st[2 * B + lb] = 1                                  # hist_len
-            st[3 * B + lb] = torch.tensor([x[2] for x in live], dtype=torch.int32, device=dev)
-            cur[lb] = fi
-            hist[0, lb] = fi
-            for b, _, _ in live:
-                count_h[b] = 1
-
-    RAGGED_MAX_ROWS = 8192      # packed rows of one vcla_llama_extend_rows call (its workspace is sized for them); longer passes are cut
-
-    def _inflight_admit_ragged(self, g, reqs, sched, eos, samp_kw, uni, kv, km, st, hist, cur, count_h, share, per=None, lp=None) -> None:
-        """share_prefix=True: the requests admitted at one boundary, every one at position 0 of its slot.  In the passes of prefix.passes: copy
-        the rows [0, P_i) each request reuses from the pool into its slot (one indexed copy per pass), run the vision stack over the images
-        that are needed, then ONE vcla_llama_extend_rows over the rows [P_i, T_i) of all of them, written straight into the slots; the
-        creators of the pass then leave their leading rows in the pool (one indexed copy)."""
-        from . import prefix
-        dev = self._device
-        B = sched.slots
-        plan, pool = share["plan"], share["pool"]
-        P, vis_needed, pstate = share["P"], share["vis"], share["pstate"]   # without a prefix cache: plan.P, plan.vision_needed, None
-        cached = pstate["from_cache"] if pstate is not None else [False] * len(P)
-        slot_of = dict(zip(g.requests, g.slots))
-        Q = self.config.visual_resampler_config["num_query_tokens"]
-        first_of: Dict[int, int] = {}
-
-        def index(pairs):                                       # [(slot, first row, pool rows)] -> (pool idx, slot idx, row idx) on the device
-            pi = torch.tensor([x for _, _, rows in pairs for x in rows], device=dev)
-            si = torch.tensor([b for b, _, rows in pairs for _ in rows], device=dev)
-            ri = torch.tensor([r0 + k for _, r0, rows in pairs for k in range(len(rows))], device=dev)
-            return pi, si, ri
-        for members in prefix.passes(plan, g.requests):
-            share["passes"] += 1
-            reads = [(slot_of[i], 0, share["rows"][plan.source[i]][:P[i]]) for i in members if P[i] > 0 and not cached[i]]
-            if reads:
-                pi, si, ri = index(reads)
-                kv[:, :, si, :, ri] = pool[pi]
-            if pstate is not None:                              # the rows the prefix cache holds: its blocks into the slots, one launch
-                _lib.kv_blocks_copy(kv, pstate["cache"].pool, pstate["cache"].read_entries(pstate, members, slot_of), to_pool=False)
-            # ---- embeddings of whole prompts, by classes of equal (length, image, vision needed): one check and one splice per class
-            classes: Dict[tuple, List[int]] = {}
-            for i in members:
-                classes.setdefault((int(reqs[i]["ids"].numel()), reqs[i]["px"] is not None, vis_needed[i]), []).append(i)
-            emb_of: Dict[int, torch.Tensor] = {}
-            for (T, has_px, vis), cls in classes.items():
-                ids = torch.stack([reqs[i]["ids"] for i in cls])
-                img_pos, _ = self._check_request(ids, None, Q if has_px else 0, for_generate=True)
-                img = None
-                if vis:
-                    img = self.embed_images(torch.stack([reqs[i]["px"] for i in cls]))
-                    share["vision"] += len(cls)
-                embeds, _ = self._embed(ids, img, img_pos if vis else None)
-                for j, i in enumerate(cls):
-                    emb_of[i] = embeds[j, P[i]:]
-            # ---- the rows behind the shared prefixes, cut into calls of at most RAGGED_MAX_ROWS rows (a block the kernel does not take goes alone)
-            calls, cur_call, m = [], [], 0
-            for i in members:
-                r = plan.T[i] - P[i]
-                alone = r > _lib.EXTEND_MAX_ROWS
-                if cur_call and (alone or m + r > self.RAGGED_MAX_ROWS):
-                    calls.append(cur_call)
-                    cur_call, m = [], 0
-                cur_call.append(i)
-                m += r
-                if alone:
-                    calls.append(cur_call)
-                    cur_call, m = [], 0
-            if cur_call:
-                calls.append(cur_call)
-            for call in calls:
-                table = [(slot_of[i], P[i], plan.T[i] - P[i]) for i in call]
-                logits = self._extend_rows(torch.cat([emb_of[i] for i in call]), table, kv,
-                                           ws_for=(min(self.RAGGED_MAX_ROWS, B * max(plan.T)), B))
-                share["calls"] += 1
-                if self._inflight_logits_tap is not None:
-                    self._inflight_logits_tap.append((list(call), logits.detach().clone()))
-                sl = torch.tensor([slot_of[i] for i in call], device=dev)
-                km[sl] = 1
-                first = self._inflight_first(logits, call, sl, samp_kw, uni, per, hist, lp)
-                for i, tok in zip(call, first.tolist()):          # synchronises
-                    first_of[i] = tok
-            share["reused"] += sum(P[i] for i in members)
-            share["computed"] += sum(plan.T[i] - P[i] for i in members)
-            # ---- the creators of this pass leave their rows in the pool; entries whose last reader this pass held are released
-            made = []
-            for i in members:
-                e = plan.entries.get(i)
-                if e is not None:
-                    share["rows"][i] = [share["free"].pop() for _ in range(e.rows)]
-                    made.append((slot_of[i], 0, share["rows"][i]))
-            if made:
-                pi, si, ri = index(made)
-                pool[pi] = kv[:, :, si, :, ri]
-            for i in members:
-                s_ = plan.source[i]
-                if s_ is not None and plan.entries[s_].last_reader == i:
-                    share["free"].extend(share["rows"].pop(s_))
-            if pstate is not None:                              # the members' full blocks that the prefix cache lacks: out of the slots, one launch
-                _lib.kv_blocks_copy(kv, pstate["cache"].pool, pstate["cache"].insert_entries(pstate, members, slot_of), to_pool=True)
-        live = []
-        for i, b in zip(g.requests, g.slots):
-            ended = first_of[i] in (eos if per is None else per["eos_of"][i]) or sched.budget[i] == 1
-            sched.started(b, first_of[i], ended, lp["first"].pop(i) if lp is not None else None)
-            if not ended:
-                live.append((b, first_of[i], sched.budget[i], plan.T[i]))
-        if live:
-            lb = torch.tensor([x[0] for x in live], device=dev)
-            fi = torch.tensor([x[1] for x in live], dtype=torch.int64, device=dev)
-            st[lb] = torch.tensor([x[3] for x in live], dtype=torch.int32, device=dev)        # row_pos: every slot decodes from its own T
-            st[B + lb] = 1                                      # count
-            st[2 * B + lb] = 1                                  # hist_len
-            st[3 * B + lb] = torch.tensor([x[2] for x in live], dtype=torch.int32, device=dev)
-            cur[lb] = fi
-            hist[0, lb] = fi
-            for b, _, _, _ in live:
-                count_h[b] = 1

@@ -1,0 +1,415 @@
+"""The slots loop of VisualCLAModel.generate_many (DESIGN.md sections 7c-7h): one SlotsRun per call holds the buffers, the scheduler and
+what the features switched on add -- PerRequest (per-slot eos lists and sampler records, 7f), Logprobs (7h), PrefixShare (7e, 7g); None
+where the feature is off -- and admits, steps and harvests until the queue is empty.  The model (`self.m`) keeps its kernels' wrappers."""
+from __future__ import annotations
+
+import ctypes as C
+import time
+from typing import Dict, List, Optional
+
+import torch
+
+from . import _lib, prefix
+
+RAGGED_MAX_ROWS = 8192      # packed rows of one vcla_llama_extend_rows call (its workspace is sized for them); longer passes are cut
+
+
+class PerRequest:
+    """requests under different configs: eos_of[i] / kw_of[i] are request i's eos list and its vcla_sample_row fields, do_sample[i] whether
+    it draws; eos_dev int32 [B, SLOT_MAX_EOS] and rows_dev uint8 [B, 64] (None: no request needs the sampler) are the per-slot tables"""
+    __slots__ = ("eos_of", "kw_of", "eos_dev", "rows_dev", "do_sample")
+
+    def __init__(self, eos_of: List[List[int]], kw_of: List[dict], eos_dev: torch.Tensor, rows_dev: Optional[torch.Tensor], do_sample: List[bool]):
+        self.eos_of, self.kw_of, self.eos_dev, self.rows_dev, self.do_sample = eos_of, kw_of, eos_dev, rows_dev, do_sample
+
+
+class Logprobs:
+    """logprobs=k: the [cap, B(, k)] columns the step writes (top_* None at k = 0; forced None unless a request has target_ids), the step's
+    vcla_logprob_args over them, and first[i]: the arrays of admitted request i's first token until its slot starts"""
+    __slots__ = ("k", "lp", "top_ids", "top_lp", "forced", "first", "args")
+
+    def __init__(self, k: int, lp: torch.Tensor, top_ids: Optional[torch.Tensor], top_lp: Optional[torch.Tensor], forced: Optional[torch.Tensor], args):
+        self.k, self.lp, self.top_ids, self.top_lp, self.forced, self.first, self.args = k, lp, top_ids, top_lp, forced, {}, args
+
+
+class PrefixShare:
+    """share_prefix=True: the plan, this call's pool [rows, L, 2, H, d] with its free rows and the rows every creator holds, the rows P[i]
+    request i reuses and whether its image needs the vision stack (as the plan and a prefix cache's `pstate` combine), the counters"""
+    __slots__ = ("plan", "pool", "free", "rows", "P", "vis", "pstate", "reused", "computed", "vision", "passes", "calls")
+
+    def __init__(self, plan, pool: torch.Tensor, pstate: Optional[dict]):
+        self.plan, self.pool, self.pstate, self.rows, self.free = plan, pool, pstate, {}, list(range(pool.shape[0] - 1, -1, -1))
+        self.P, self.vis = (plan.P, plan.vision_needed) if pstate is None else (pstate["P"], pstate["vision"])   # (prefix_cache.combine)
+        self.reused = self.computed = self.vision = self.passes = self.calls = 0
+
+
+def _prefix_plan(model, reqs, slots: int, pool_rows: Optional[int], keys=None, prompts=None):
+    """the prefix plan of a queue (visualcla/prefix.py) from its ids and images (keys / prompts: _image_keys / _prompt_lists of the queue, when the caller needs them too)"""
+    if pool_rows is not None and int(pool_rows) < 0:
+        raise ValueError(f"prefix_pool_tokens must be >= 0 (got {pool_rows})")
+    keys = _image_keys(model, reqs) if keys is None else keys
+    prompts = _prompt_lists(reqs) if prompts is None else prompts
+    return prefix.plan(prompts, keys, model._special_ids()[2] if any(k is not None for k in keys) else None, slots, pool_rows)
+
+
+def _prompt_lists(reqs):
+    """the ids of every request as host lists (one copy back when the prompts have one length)"""
+    return [r["ids"].tolist() for r in reqs] if len({int(r["ids"].numel()) for r in reqs}) != 1 else torch.stack([r["ids"] for r in reqs]).tolist()
+
+
+def _image_keys(model, reqs):
+    """one key per request, None without an image, equal for equal images: the index of the first request that carries the image.
+    Images are compared BY VALUE, as the vision stack sees them (model dtype), inside this pass: one fingerprint per image (a launch
+    over the stacked images, one copy back) buckets them, one row-wise comparison of every image with the first of its bucket
+    confirms (a second copy back); the same tensor object needs neither."""
+    keys: List[Optional[int]] = [None] * len(reqs)
+    with_px = [i for i, r in enumerate(reqs) if r["px"] is not None]
+    by_obj: Dict[int, int] = {}
+    firsts = []                                               # the first request of every distinct tensor object
+    for i in with_px:
+        if by_obj.setdefault(id(reqs[i]["px"]), i) == i:
+            firsts.append(i)
+    by_shape: Dict[tuple, List[int]] = {}
+    for i in firsts:
+        by_shape.setdefault(tuple(reqs[i]["px"].shape), []).append(i)
+    for members in by_shape.values():
+        flat = torch.stack([reqs[i]["px"].to(model._dtype) for i in members]).flatten(1)
+        w = torch.linspace(1.0, 2.0, flat.shape[1], device=flat.device, dtype=torch.float32)
+        prints = torch.stack([flat.float().sum(1), (flat.float() * w).sum(1)], dim=1).tolist()
+        rep_of: Dict[tuple, int] = {}
+        cand = [rep_of.setdefault(tuple(fp), k) for k, fp in enumerate(prints)]
+        same = (flat == flat[torch.tensor(cand, device=flat.device)]).all(dim=1).tolist()
+        for k, i in enumerate(members):
+            keys[i] = members[cand[k]] if same[k] else i      # (a fingerprint collision of different images: a key of its own)
+    for i in with_px:
+        keys[i] = keys[by_obj[id(reqs[i]["px"])]]
+    return keys
+
+
+def _per_request_tables(model, gcs, sched) -> PerRequest:
+    """Requests under different configs: what the slots loop needs beside the queue-wide state.  The captured step reads
+    the tables (rows_dev None: the step is argmax + the per-row eos lookup).  A greedy request is a record with top_k = 1 and the greedy flag."""
+    B = sched.slots
+    eos_of = [model._eos_list(g) for g in gcs]
+    kw_by_cfg: Dict[int, Optional[dict]] = {}
+    table = any(model._uses_sampler(g) for g in gcs)
+    kw_of = []
+    for i, g in enumerate(gcs):
+        if id(g) not in kw_by_cfg:
+            kw = None
+            if model._uses_sampler(g):
+                kw = model._device_sampling(g, max(sched.budget[j] for j, h in enumerate(gcs) if h is g), 0)
+                if kw is None:
+                    raise ValueError(f"generate_many: the generation config of request {i} does not map onto the device sampler")
+            kw_by_cfg[id(g)] = dict(kw or {}, greedy=not g.do_sample)
+        kw_of.append(kw_by_cfg[id(g)])
+    if table:
+        _lib.sample_row_table(kw_of)                          # range checks of every record, before any kernel runs
+    eos_dev = model._typed_buf("if_eos_rows", (B, _lib.SLOT_MAX_EOS), torch.int32).fill_(-1)
+    rows_dev = model._typed_buf("if_sample_rows", (B, C.sizeof(_lib.SampleRow)), torch.uint8) if table else None
+    if table:
+        rows_dev.copy_(_lib.sample_row_bytes(_lib.sample_row_table([dict(greedy=True)] * B)))
+    return PerRequest(eos_of, kw_of, eos_dev, rows_dev, [bool(g.do_sample) for g in gcs])
+
+
+def cut_calls(rows_of, members, max_rows: int, alone_above: int) -> List[List[int]]:
+    """`members` in order, cut into calls of at most max_rows rows (member i brings rows_of[i]); a member of more than alone_above rows
+    (a block the kernel does not take) goes alone"""
+    calls, m, closed = [], 0, True
+    for i in members:
+        if closed or rows_of[i] > alone_above or m + rows_of[i] > max_rows:
+            calls.append([])
+            m = 0
+        calls[-1].append(i)
+        m += rows_of[i]
+        closed = rows_of[i] > alone_above
+    return calls
+
+
+class SlotsRun:
+    """gcs None: one config `gc` for the whole queue.  Else gcs[i] is request i's config, there are at least two distinct ones, and the
+    step reads per-slot tables (_per_request_tables).  pstate: the call's state of a prefix cache (PrefixCache.begin), or None.
+    logprobs (k or None): the step also runs the stats pass and the pick (csrc/logprobs.hip); sched.targets[i] forces request i."""
+
+    def __init__(self, model, gc, reqs, sched, use_graph, plan=None, gcs=None, seeds=None, pstate=None, logprobs=None):
+        self.m, self.reqs, self.sched, self.use_graph, self.dev = model, reqs, sched, use_graph, model._device
+        self.lib = lib = _lib.load()
+        t, B, ctx_max, cap, W = model.config.text_config, sched.slots, sched.ctx_max, sched.cap, _lib.SLOT_SUMMARY_WORDS
+        self.seeds = seeds if seeds is not None else [None] * sched.n
+        self.per = per = _per_request_tables(model, gcs, sched) if gcs is not None else None
+        self.eos = eos = model._eos_list(gc) if per is None else []
+        samp_kw = None
+        if per is not None:
+            samp_kw = {} if per.rows_dev is not None else None     # the scalar fields of the shared block are ignored by the table entry
+        elif model._uses_sampler(gc):
+            samp_kw = model._device_sampling(gc, cap, 0)
+            if samp_kw is None:
+                raise ValueError("generate_many: the generation config does not map onto the device sampler")
+        self.samp_kw = samp_kw
+        draws = [bool(gc.do_sample)] * sched.n if per is None else per.do_sample
+        self.draws = draws = [d and tg is None for d, tg in zip(draws, sched.targets)]     # a forced request draws no uniforms
+        # ---- the slot table: one int32 vector (row_pos | count | hist_len | budget | summary) so that a boundary is ONE copy to the host
+        self.st = st = model._typed_buf("if_state", (4 * B + W,), torch.int32)
+        st.copy_(torch.tensor([-1] * B + [0] * B + [-1] * B + [0] * B + [0] * W, dtype=torch.int32))
+        row_pos, count, hist_len, budget, summary = st[:B], st[B:2 * B], st[2 * B:3 * B], st[3 * B:4 * B], st[4 * B:]
+        self.hist = hist = model._typed_buf("if_hist", (cap, B), torch.int64)
+        self.cur = cur = model._typed_buf("if_cur", (B,), torch.int64).zero_()
+        self.uni = uni = model._typed_buf("if_uni", (cap, B), torch.float32) if any(draws) and samp_kw is not None else None
+        H, d = t["num_attention_heads"], t["hidden_size"] // t["num_attention_heads"]
+        self.kv = model._typed_buf("if_kv", (t["num_hidden_layers"], 2, B, H, ctx_max, d), model._dtype)
+        self.km = model._typed_buf("if_km", (B, ctx_max), torch.int32).fill_(1)
+        self.lp = None
+        ws_bytes = lib.vcla_llama_workspace_bytes(model._ctx, B, 1)
+        if logprobs is not None:
+            k = int(logprobs)
+            ws_bytes += lib.vcla_logprob_scratch_bytes(B, t["vocab_size"], int(samp_kw is not None))
+            bufs = (model._typed_buf("if_lp", (cap, B), torch.float32),
+                    model._typed_buf("if_top_ids", (cap, B, k), torch.int64) if k else None,
+                    model._typed_buf("if_top_lp", (cap, B, k), torch.float32) if k else None,
+                    model._typed_buf("if_forced", (cap, B), torch.int64).fill_(-1) if any(tg is not None for tg in sched.targets) else None)
+            self.lp = Logprobs(k, *bufs, _lib.logprob_args(k, *bufs))
+        self.ws = model._buf("slots", ws_bytes)
+        self.slot_args = _lib.slot_args(eos, row_pos, count, budget, hist_len, hist, cur, summary)
+        self.samp = _lib.sample_args(uniforms=uni, history=hist, **samp_kw) if samp_kw is not None else None
+        self.count_h, self.share = [0] * B, None
+        if plan is not None:                                    # the prefix pool of this call: [rows, L, 2, H, d], 2 L H d elements per row
+            n_rows = min(plan.pool_rows, plan.peak_pool_rows)
+            self.share = PrefixShare(plan, torch.empty(n_rows, t["num_hidden_layers"], 2, H, d, dtype=model._dtype, device=self.dev), pstate)
+
+    def run(self):
+        """admit, step and harvest until the queue is empty -> the results in request order; sets model.last_inflight_stats"""
+        sched, share, t_adm, t_steps = self.sched, self.share, 0.0, 0.0
+        while not sched.finished:
+            t0 = time.perf_counter()
+            while groups := sched.admit(sched.free_slots()):    # (again: a request whose first token ends it frees its slot within the boundary)
+                if self.uni is not None:
+                    self.draw_uniforms(groups)
+                if self.lp is not None and self.lp.forced is not None:
+                    self.fill_forced(groups)
+                for g in groups:
+                    if self.per is not None:
+                        self.fill_rows(g.requests, g.slots)
+                    (self.admit_ragged if g.ragged else self.admit_padded)(g)
+            t1 = time.perf_counter()
+            t_adm += t1 - t0
+            if sched.finished:
+                break
+            self.decode_chunk(sched.steps_per_sync)
+            self.harvest(self.st.tolist())                      # the one synchronisation of the boundary: positions, counts, n_active
+            t_steps += time.perf_counter() - t1
+        # beside the counters: host seconds spent in admission / in steps, and the position every request's slot decoded from (its group's longest prompt)
+        self.m.last_inflight_stats = stats = dict(sched.stats, admission_s=t_adm, steps_s=t_steps, ctx_max=sched.ctx_max, decode_from=[sched.decode_from[i] for i in range(sched.n)])
+        if share is not None:
+            stats.update(rows_reused=share.reused, rows_computed=share.computed, vision_runs=share.vision, pool_entries=len(share.plan.entries),
+                         pool_bytes=share.pool.numel() * share.pool.element_size(), pool_rows=int(share.pool.shape[0]),
+                         admission_passes=share.passes, rows_calls=share.calls,
+                         workspace_bytes=int(self.m._ws["extend_rows"].numel()) if "extend_rows" in self.m._ws else 0)
+        out = sched.ordered_results()                           # with logprobs RequestOutput tuples of lists: generate_many makes the tensors
+        return out if self.lp is not None else [torch.tensor(toks, dtype=torch.int64, device=self.dev) for toks in out]
+
+    def draw_uniforms(self, groups) -> None:
+        """request i's own column of uniforms, in request order; with a `seed` a function of (seed, budget) alone, whatever else is in the queue"""
+        for i, b in sorted((i, b) for g in groups for i, b in zip(g.requests, g.slots)):
+            if self.draws[i]:                                   # (a greedy row of the table draws at 0)
+                gen = torch.Generator(device=self.dev).manual_seed(int(self.seeds[i])) if self.seeds[i] is not None else None
+                self.uni[:self.sched.budget[i], b] = torch.rand(self.sched.budget[i], device=self.dev, generator=gen)
+
+    def fill_forced(self, groups) -> None:
+        """the forced column of every slot that is filled: -1 = free-running"""
+        sched, forced = self.sched, self.lp.forced
+        for g in groups:
+            for i, b in zip(g.requests, g.slots):
+                forced[:, b] = -1
+                if sched.targets[i] is not None:
+                    forced[:sched.budget[i], b] = torch.tensor(sched.targets[i], dtype=torch.int64, device=self.dev)
+
+    def fill_rows(self, requests, slots) -> None:
+        """admission: the table rows of the slots it fills, rewritten between two chunks of steps"""
+        per = self.per
+        sl = torch.tensor(list(slots), device=self.dev)
+        per.eos_dev[sl] = _lib.slot_eos_rows([per.eos_of[i] for i in requests]).to(self.dev)
+        if per.rows_dev is not None:
+            per.rows_dev[sl] = _lib.sample_row_bytes(_lib.sample_row_table([per.kw_of[i] for i in requests]), len(requests)).to(self.dev)
+
+    def first_token(self, logits, requests, sl):
+        """the first token of the requests whose prefill produced `logits` (row j = requests[j], slot sl[j]): the same selector as the steps,
+        at history length 0 -- argmax, the uniform sampler, or the table entry with the admitted requests' own records.  logprobs: the stats pass over
+        the raw logits before it (a sampler then works on the copy), the pick with the requests' forced[0] behind it; into row 0 of the slots' columns and lp.first"""
+        per, lp, dev, G = self.per, self.lp, self.dev, len(requests)
+
+        def select(x):                                          # (`x` is modified by a sampler)
+            u0 = self.uni[0, sl].view(1, G).contiguous() if self.uni is not None else None
+            if per is not None and per.rows_dev is not None:
+                rows = _lib.sample_row_bytes(_lib.sample_row_table([per.kw_of[i] for i in requests]), G).to(dev)
+                return _lib.sample_rows_table(x, torch.zeros(G, dtype=torch.int32, device=dev), _lib.sample_args(uniforms=u0, history=self.hist), rows)
+            if self.samp_kw is None:
+                return _lib.argmax(x)
+            return _lib.sample(x, _lib.sample_args(uniforms=u0, **self.samp_kw), n_hist=0)
+        if lp is None:
+            return select(logits)
+        k = lp.k
+        zeros = torch.zeros(G, dtype=torch.int32, device=dev)
+        t_lp = torch.empty(1, G, dtype=torch.float32, device=dev)
+        t_ids = torch.empty(1, G, k, dtype=torch.int64, device=dev) if k else None
+        t_top = torch.empty(1, G, k, dtype=torch.float32, device=dev) if k else None
+        f0 = lp.forced[0, sl].view(1, G).contiguous() if lp.forced is not None else None
+        args = _lib.logprob_args(k, t_lp, t_ids, t_top, f0)
+        work = torch.empty_like(logits) if self.samp_kw is not None else None     # the sampler modifies its input; the gather needs the raw rows
+        lse = _lib.logprob_rows(logits, zeros, args, 1, copy=work)
+        first = select(logits if work is None else work)
+        _lib.logprob_pick(logits, zeros, args, 1, lse, first)
+        lp.lp[0, sl] = t_lp[0]
+        if k:
+            lp.top_ids[0, sl] = t_ids[0]
+            lp.top_lp[0, sl] = t_top[0]
+        a, b_, c = t_lp[0].tolist(), (t_ids[0].tolist() if k else [[]] * G), (t_top[0].tolist() if k else [[]] * G)
+        for j, i in enumerate(requests):
+            lp.first[i] = ([a[j]], [b_[j]], [c[j]])
+        return first
+
+    def start_slots(self, requests, slots, first_tokens, row_pos_of) -> None:
+        """the tail of an admission: first_tokens[j] came out of the prefill of requests[j] in slots[j].  A request it ends (an eos, a budget of 1) never
+        occupies the slot; the others get their slot state.  row_pos_of: where the slots decode from -- one int (a left-padded group) or a table by request"""
+        sched, st, B, live = self.sched, self.st, self.sched.slots, []
+        for i, b, tok in zip(requests, slots, first_tokens):
+            ended = tok in (self.eos if self.per is None else self.per.eos_of[i]) or sched.budget[i] == 1
+            sched.started(b, tok, ended, self.lp.first.pop(i) if self.lp is not None else None)
+            if not ended:
+                live.append((i, b, tok))
+        if live:
+            lb = torch.tensor([b for _, b, _ in live], device=self.dev)
+            fi = torch.tensor([tok for _, _, tok in live], dtype=torch.int64, device=self.dev)
+            st[lb] = torch.tensor([row_pos_of[i] for i, _, _ in live], dtype=torch.int32, device=self.dev) if hasattr(row_pos_of, "__getitem__") else row_pos_of
+            st[B + lb] = 1                                      # count
+            st[2 * B + lb] = 1                                  # hist_len
+            st[3 * B + lb] = torch.tensor([sched.budget[i] for i, _, _ in live], dtype=torch.int32, device=self.dev)
+            self.cur[lb] = fi
+            self.hist[0, lb] = fi
+            for _, b, _ in live:
+                self.count_h[b] = 1
+
+    def admit_padded(self, g) -> None:
+        """One admission group through the request path of generate() as a left-padded batch (checks, vision stack, embedding splice, prefill
+        into a private cache), then into its slots: K/V rows [0, T_group), the pad holes of the key mask, the first token, the slot state."""
+        m, dev = self.m, self.dev
+        rs = [self.reqs[i] for i in g.requests]
+        G, Tt = len(rs), max(int(r["ids"].numel()) for r in rs)
+        ids = torch.zeros(G, Tt, dtype=torch.int64, device=dev)
+        am = torch.zeros(G, Tt, dtype=torch.int64, device=dev)
+        for j, r in enumerate(rs):
+            n = int(r["ids"].numel())
+            ids[j, Tt - n:] = r["ids"]
+            am[j, Tt - n:] = 1 if r["am"] is None else r["am"].to(torch.int64)
+        masked = any(r["am"] is not None or int(r["ids"].numel()) < Tt for r in rs)
+        px = torch.stack([r["px"] for r in rs]) if g.image else None
+        Q = m.config.visual_resampler_config["num_query_tokens"] if g.image else 0
+        img_pos, am2 = m._check_request(ids, am if masked else None, Q, for_generate=True)
+        img = m.embed_images(px) if px is not None else None
+        embeds, _ = m._embed(ids, img, img_pos)
+        Tg = embeds.shape[1]
+        if Tg != g.T:
+            raise ValueError(f"generate_many: group of requests {g.requests} embeds to {Tg} positions, the scheduler planned {g.T}")
+        own = m._new_cache(G, Tg)
+        logits = m._prefill(embeds, own, m._key_mask(am2, G, Tg, Tg), all_logits=False)
+        if m._inflight_logits_tap is not None:
+            m._inflight_logits_tap.append((list(g.requests), logits.detach().clone()))
+        sl = torch.tensor(g.slots, device=dev)
+        self.kv[:, :, sl, :, :Tg, :] = own.kv
+        self.km[sl] = 1
+        if am2 is not None:
+            self.km[sl, :Tg] = am2.to(torch.int32)
+        self.start_slots(g.requests, g.slots, self.first_token(logits, g.requests, sl).tolist(), Tg)      # (.tolist() synchronises)
+
+    def admit_ragged(self, g) -> None:
+        """share_prefix=True: the requests admitted at one boundary, every one at position 0 of its slot.  In the passes of prefix.passes: copy
+        the rows [0, P_i) each request reuses from the pool into its slot (one indexed copy per pass), run the vision stack over the images
+        that are needed, then ONE vcla_llama_extend_rows over the rows [P_i, T_i) of all of them, written straight into the slots; the
+        creators of the pass then leave their leading rows in the pool (one indexed copy)."""
+        m, dev, reqs, kv, sh, B = self.m, self.dev, self.reqs, self.kv, self.share, self.sched.slots
+        plan, pool, P, pstate = sh.plan, sh.pool, sh.P, sh.pstate
+        cached = pstate["from_cache"] if pstate is not None else [False] * len(P)
+        slot_of = dict(zip(g.requests, g.slots))
+        Q = m.config.visual_resampler_config["num_query_tokens"]
+        rows_of = {i: plan.T[i] - P[i] for i in g.requests}     # the rows behind its shared prefix that every request computes
+        first_of: Dict[int, int] = {}
+
+        def index(pairs):                                       # [(slot, first row, pool rows)] -> (pool idx, slot idx, row idx) on the device
+            pi = torch.tensor([x for _, _, rows in pairs for x in rows], device=dev)
+            si = torch.tensor([b for b, _, rows in pairs for _ in rows], device=dev)
+            ri = torch.tensor([r0 + k for _, r0, rows in pairs for k in range(len(rows))], device=dev)
+            return pi, si, ri
+        for members in prefix.passes(plan, g.requests):
+            sh.passes += 1
+            reads = [(slot_of[i], 0, sh.rows[plan.source[i]][:P[i]]) for i in members if P[i] > 0 and not cached[i]]
+            if reads:
+                pi, si, ri = index(reads)
+                kv[:, :, si, :, ri] = pool[pi]
+            if pstate is not None:                              # the rows the prefix cache holds: its blocks into the slots, one launch
+                _lib.kv_blocks_copy(kv, pstate["cache"].pool, pstate["cache"].read_entries(pstate, members, slot_of), to_pool=False)
+            # ---- embeddings of whole prompts, by classes of equal (length, image, vision needed): one check and one splice per class
+            classes: Dict[tuple, List[int]] = {}
+            for i in members:
+                classes.setdefault((int(reqs[i]["ids"].numel()), reqs[i]["px"] is not None, sh.vis[i]), []).append(i)
+            emb_of: Dict[int, torch.Tensor] = {}
+            for (T, has_px, vis), cls in classes.items():
+                ids = torch.stack([reqs[i]["ids"] for i in cls])
+                img_pos, _ = m._check_request(ids, None, Q if has_px else 0, for_generate=True)
+                img = m.embed_images(torch.stack([reqs[i]["px"] for i in cls])) if vis else None
+                sh.vision += len(cls) if vis else 0
+                embeds, _ = m._embed(ids, img, img_pos if vis else None)
+                for j, i in enumerate(cls):
+                    emb_of[i] = embeds[j, P[i]:]
+            for call in cut_calls(rows_of, members, RAGGED_MAX_ROWS, _lib.EXTEND_MAX_ROWS):
+                table = [(slot_of[i], P[i], rows_of[i]) for i in call]
+                logits = m._extend_rows(torch.cat([emb_of[i] for i in call]), table, kv, ws_for=(min(RAGGED_MAX_ROWS, B * max(plan.T)), B))
+                sh.calls += 1
+                if m._inflight_logits_tap is not None:
+                    m._inflight_logits_tap.append((list(call), logits.detach().clone()))
+                sl = torch.tensor([slot_of[i] for i in call], device=dev)
+                self.km[sl] = 1
+                first_of.update(zip(call, self.first_token(logits, call, sl).tolist()))      # (.tolist() synchronises)
+            sh.reused += sum(P[i] for i in members)
+            sh.computed += sum(rows_of[i] for i in members)
+            # ---- the creators of this pass leave their rows in the pool; entries whose last reader this pass held are released
+            made = []
+            for i in members:
+                e = plan.entries.get(i)
+                if e is not None:
+                    sh.rows[i] = [sh.free.pop() for _ in range(e.rows)]
+                    made.append((slot_of[i], 0, sh.rows[i]))
+            if made:
+                pi, si, ri = index(made)
+                pool[pi] = kv[:, :, si, :, ri]
+            for i in members:
+                s_ = plan.source[i]
+                if s_ is not None and plan.entries[s_].last_reader == i:
+                    sh.free.extend(sh.rows.pop(s_))
+            if pstate is not None:                              # the members' full blocks that the prefix cache lacks: out of the slots, one launch
+                _lib.kv_blocks_copy(kv, pstate["cache"].pool, pstate["cache"].insert_entries(pstate, members, slot_of), to_pool=True)
+        self.start_slots(g.requests, g.slots, [first_of[i] for i in g.requests], plan.T)      # every slot decodes from its own T
+
+    def decode_chunk(self, n: int) -> None:
+        """n steps of every live slot, one call; the per-slot tables and the logprob block are null where the feature is off"""
+        per, ws = self.per, self.ws
+        _lib.check(self.lib.vcla_llama_decode_slots_logprobs(
+            self.m._ctx, C.byref(self.slot_args), n, self.kv.data_ptr(), self.sched.ctx_max, self.km.data_ptr(), ws.data_ptr(), ws.numel(),
+            int(self.use_graph), C.byref(self.samp) if self.samp is not None else None, per.eos_dev.data_ptr() if per is not None else None,
+            _lib.ptr(per.rows_dev) if per is not None else None, C.byref(self.lp.args) if self.lp is not None else None, _lib.stream_ptr()))
+
+    def harvest(self, host) -> None:
+        """`host`: the slot table after a chunk.  The finished slots' columns of the history and of the logprob buffers go to the scheduler"""
+        sched, lp, B = self.sched, self.lp, self.sched.slots
+        pos_h, cnt_h = host[:B], host[B:2 * B]
+        done = [b for b in range(B) if sched.slot_req[b] is not None and pos_h[b] < 0]
+        di = torch.tensor(done, device=self.dev) if done else None
+        cols = dict(zip(done, self.hist[:, di].t().tolist())) if done else {}
+        extras_of = None
+        if lp is not None:
+            lcols = dict(zip(done, lp.lp[:, di].t().tolist())) if done else {}
+            icols = dict(zip(done, lp.top_ids[:, di].permute(1, 0, 2).tolist())) if done and lp.k else None
+            tcols = dict(zip(done, lp.top_lp[:, di].permute(1, 0, 2).tolist())) if done and lp.k else None
+
+            def extras_of(b, m):
+                return lcols[b][:m], (icols[b][:m] if icols is not None else [[]] * m), (tcols[b][:m] if tcols is not None else [[]] * m)
+        sched.after_chunk(sched.steps_per_sync, pos_h, cnt_h, lambda b, m: cols[b][:m], self.count_h, extras_of)
+        self.count_h = cnt_h
