@@ -737,6 +737,60 @@ int vcla_llama_decode_slots_logprobs(vcla_ctx* ctx, const vcla_slot_args* slots,
                                      const int32_t* key_mask, void* ws, size_t ws_bytes, int use_graph, const vcla_sample_args* sampling,
                                      const int32_t* eos_rows, const vcla_sample_row* rows, const vcla_logprob_args* logprobs, void* stream);
 
+/* ---------------------------------------------------------------- per-request token constraints decided on the device (slots)
+   HF restricts what a request may generate through host callbacks inside its per-token loop: PrefixConstrainedLogitsProcessor
+   (`prefix_allowed_tokens_fn`) and SuppressTokensLogitsProcessor (hf:generation/logits_process.py, reached from
+   models/visualcla/modeling_visualcla.py:382-391).  Where the callback is static data -- an allow list, a ban list, a trie of candidate
+   answers -- it is a token AUTOMATON in device memory, applied and advanced inside the step: no host round trip, the captured graph is
+   kept.  One flat table per call (visualcla/constraints.py builds and validates it): node s owns the edges [edge0, edge0 + n_edges),
+   sorted by token; an ALLOW node keeps exactly its edges' tokens and moves along the edge taken, a DENY node drops exactly its edges'
+   tokens and never moves.  Caps of one table: VCLA_CS_MAX_NODES nodes, VCLA_CS_MAX_EDGES edges (8 MiB); a row's token set is a bitmask
+   in 64 KiB of LDS: V <= VCLA_CS_MAX_VOCAB.  Additive entries; the ABI version stays 5. */
+#define VCLA_CS_MAX_NODES 65536
+#define VCLA_CS_MAX_EDGES 1048576
+#define VCLA_CS_MAX_VOCAB 524288
+typedef struct vcla_cs_node {
+    int32_t edge0;               /* first edge of the node in the edge table                                                         */
+    int32_t n_edges;             /* >= 1                                                                                             */
+    int32_t deny;                /* 0: allow node (keep the edges' tokens, follow the edge taken); 1: deny node (drop them, stay)    */
+    int32_t pad;
+} vcla_cs_node;
+typedef struct vcla_cs_edge {
+    int32_t token;               /* 0 .. V - 1, ascending inside a node, no token twice                                              */
+    int32_t next;                /* node the state moves to when an allow node takes `token`                                         */
+} vcla_cs_edge;
+typedef struct vcla_constrain_args {
+    const vcla_cs_node* nodes;   /* [n_nodes] device memory                                                                          */
+    const vcla_cs_edge* edges;   /* [n_edges] device memory                                                                          */
+    int32_t* state;              /* [B] device memory: the node of every row; < 0: the row is unconstrained                          */
+    int32_t n_nodes, n_edges;
+} vcla_constrain_args;
+
+/* The mask, BEFORE the selector (the constant-function instance of PrefixConstrainedLogitsProcessor.__call__ /
+   SuppressTokensLogitsProcessor.__call__, hf:generation/logits_process.py): for every row b with n_hist_rows[b] >= 0 and
+   0 <= args->state[b], over logits[b][0 .. V) (fp32, row stride ld >= V, modified in place; columns at or behind V are neither read
+   nor written): x[j] = -inf unless the node keeps j.  Other rows are bitwise untouched.  One workgroup per row; an unconstrained row
+   costs one load.  V <= VCLA_CS_MAX_VOCAB. */
+int vcla_constrain_rows(float* logits, int64_t ld, int B, int V, const int32_t* n_hist_rows, const vcla_constrain_args* args, void* stream);
+
+/* The transition, AFTER the selector (and after vcla_logprob_pick, before vcla_slot_step): for every row as above whose node is an
+   allow node, ids[b] is looked up among the node's edges: a hit sets args->state[b] to the edge's `next`; a miss -- the id 0 an
+   all -inf row takes -- leaves the state where it is, as does a deny node.  (What a trie callback of prefix_allowed_tokens_fn
+   recomputes from input_ids at every step, hf:generation/logits_process.py PrefixConstrainedLogitsProcessor.) */
+int vcla_constrain_advance(const int64_t* ids, int B, const int32_t* n_hist_rows, const vcla_constrain_args* args, void* stream);
+
+/* vcla_llama_decode_slots_logprobs plus constraints (the per-token loop of models/visualcla/modeling_visualcla.py:382-391 with a
+   prefix_allowed_tokens_fn): constraints NULL is that function, launch for launch.  Otherwise every step runs vcla_constrain_rows at
+   slots->hist_len (required) on the row the selector reads, and vcla_constrain_advance on the ids taken, before the bookkeeping.
+   Without logprobs the mask is applied in place on the lm_head's logits.  With logprobs the stats pass writes the copy also on the
+   argmax path, the mask and the selector act on the copy, and the gather reads the raw logits:
+   ws_bytes >= vcla_llama_workspace_bytes(ctx, B, 1) + vcla_logprob_scratch_bytes(B, vocab, 1).  A has-constraints flag and the bytes
+   of *constraints are part of the graph key: a capture without constraints is never replayed for a call with them, nor the reverse. */
+int vcla_llama_decode_slots_constrained(vcla_ctx* ctx, const vcla_slot_args* slots, int n_steps, void* kv_cache, int ctx_max,
+                                        const int32_t* key_mask, void* ws, size_t ws_bytes, int use_graph, const vcla_sample_args* sampling,
+                                        const int32_t* eos_rows, const vcla_sample_row* rows, const vcla_logprob_args* logprobs,
+                                        const vcla_constrain_args* constraints, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

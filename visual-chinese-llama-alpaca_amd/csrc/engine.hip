@@ -1425,9 +1425,12 @@ extern "C" int vcla_llama_verify_loop(vcla_ctx* ctx, const vcla_lookup_args* arg
 // logprobs (vcla_llama_decode_slots_logprobs, csrc/logprobs.hip): the stats pass over the raw logits before the selector -- with a sampler it
 // also writes the copy the sampler consumes, the sampler modifies its input -- and the gather behind it; lse and the copy live behind the
 // decoder's workspace.  Part of the graph key.
-extern "C" int vcla_llama_decode_slots_logprobs(vcla_ctx* ctx, const vcla_slot_args* slots, int n_steps, void* kv_cache, int ctx_max,
-                                                const int32_t* key_mask, void* ws, size_t ws_bytes, int use_graph, const vcla_sample_args* sampling,
-                                                const int32_t* eos_rows, const vcla_sample_row* rows, const vcla_logprob_args* logprobs, void* stream) {
+// constraints (vcla_llama_decode_slots_constrained, csrc/constrain.hip): the mask on the row the selector reads -- the lm_head's logits, or
+// with logprobs the copy, which the stats pass then writes on the argmax path too -- and the transition on the ids taken.  Part of the graph key.
+extern "C" int vcla_llama_decode_slots_constrained(vcla_ctx* ctx, const vcla_slot_args* slots, int n_steps, void* kv_cache, int ctx_max,
+                                                   const int32_t* key_mask, void* ws, size_t ws_bytes, int use_graph, const vcla_sample_args* sampling,
+                                                   const int32_t* eos_rows, const vcla_sample_row* rows, const vcla_logprob_args* logprobs,
+                                                   const vcla_constrain_args* constraints, void* stream) {
     VCLA_KNOBS_SCOPE();
     VCLA_REQUIRE(ctx && ctx->finalized && ctx->c.t_layers > 0, VCLA_ERR_BAD_ARG, "llama_decode_slots: context not finalized, or vision-only");
     RUN(slot_args_check(slots, "llama_decode_slots"));
@@ -1450,11 +1453,21 @@ extern "C" int vcla_llama_decode_slots_logprobs(vcla_ctx* ctx, const vcla_slot_a
                      VCLA_ERR_BAD_ARG, "llama_decode_slots_logprobs: k=%d outside [0, %d], or a null output", logprobs->k, VCLA_LOGPROB_MAX_K);
         VCLA_REQUIRE(c.t_vocab <= VCLA_SAMPLE_MAX_VOCAB, VCLA_ERR_BAD_SHAPE, "llama_decode_slots_logprobs: vocab_size=%d (logprobs hold the row in registers: max %d)",
                      c.t_vocab, VCLA_SAMPLE_MAX_VOCAB);
-        const size_t need = ws_base + vcla_logprob_scratch_bytes(B, c.t_vocab, sampling != nullptr);
+        const bool with_copy = sampling != nullptr || constraints != nullptr;
+        const size_t need = ws_base + vcla_logprob_scratch_bytes(B, c.t_vocab, with_copy);
         VCLA_REQUIRE(ws_bytes >= need, VCLA_ERR_WORKSPACE, "llama_decode_slots_logprobs: workspace %zu < %zu bytes", ws_bytes, need);
         char* p = (char*)align256((char*)ws + ws_base);
         lp_lse = (float*)p;
-        if (sampling) lp_copy = (float*)(p + ((size_t)B * sizeof(float) + 255) / 256 * 256);
+        if (with_copy) lp_copy = (float*)(p + ((size_t)B * sizeof(float) + 255) / 256 * 256);
+    }
+    if (constraints) {
+        VCLA_REQUIRE(slots->hist_len, VCLA_ERR_BAD_ARG, "llama_decode_slots_constrained: constraints need slots->hist_len");
+        VCLA_REQUIRE(constraints->nodes && constraints->edges && constraints->state && constraints->n_nodes >= 1 && constraints->n_nodes <= VCLA_CS_MAX_NODES &&
+                         constraints->n_edges >= 1 && constraints->n_edges <= VCLA_CS_MAX_EDGES,
+                     VCLA_ERR_BAD_ARG, "llama_decode_slots_constrained: a null table, or n_nodes=%d / n_edges=%d outside 1..%d / 1..%d", constraints->n_nodes,
+                     constraints->n_edges, VCLA_CS_MAX_NODES, VCLA_CS_MAX_EDGES);
+        VCLA_REQUIRE(c.t_vocab <= VCLA_CS_MAX_VOCAB, VCLA_ERR_BAD_SHAPE, "llama_decode_slots_constrained: vocab_size=%d (the bitmask of a row lives in LDS: max %d)",
+                     c.t_vocab, VCLA_CS_MAX_VOCAB);
     }
     if (n_steps == 0) return VCLA_OK;
     hipStream_t s = (hipStream_t)stream;
@@ -1468,13 +1481,16 @@ extern "C" int vcla_llama_decode_slots_logprobs(vcla_ctx* ctx, const vcla_slot_a
         ctx->run.decode_step = true;
         RUN(decoder_rows(ctx, st, w, B, 1, 0, nullptr, kv_cache, ctx_max, key_mask, w.logits, slots->row_pos));
         if (logprobs) RUN(vcla_logprob_rows(w.logits, c.t_vocab, B, c.t_vocab, slots->hist_len, slots->hist_cap, logprobs, lp_lse, lp_copy, c.t_vocab, st));
-        if (sampling) RUN(vcla_sample_launch(lp_copy ? lp_copy : w.logits, c.t_vocab, B, c.t_vocab, 0, nullptr, sampling, w.ids, st, slots->hist_len, rows));
-        else RUN(vcla_argmax(w.logits, c.t_vocab, w.ids, B, c.t_vocab, st));
+        float* sel = lp_copy ? lp_copy : w.logits;   // the row the selector reads
+        if (constraints) RUN(vcla_constrain_rows(sel, c.t_vocab, B, c.t_vocab, slots->hist_len, constraints, st));
+        if (sampling) RUN(vcla_sample_launch(sel, c.t_vocab, B, c.t_vocab, 0, nullptr, sampling, w.ids, st, slots->hist_len, rows));
+        else RUN(vcla_argmax(sel, c.t_vocab, w.ids, B, c.t_vocab, st));
         if (logprobs) RUN(vcla_logprob_pick(w.logits, c.t_vocab, B, c.t_vocab, slots->hist_len, slots->hist_cap, logprobs, lp_lse, w.ids, st));
+        if (constraints) RUN(vcla_constrain_advance(w.ids, B, slots->hist_len, constraints, st));
         return vcla_slot_step_rows(w.ids, slots, eos_rows, ctx->embed, w.x, c.t_hidden, c.t_vocab, c.act_dtype, st);
     };
     struct { const void *kv_cache, *key_mask, *ws, *eos_rows, *rows; int ctx_max, has_samp; vcla_slot_args slots; vcla_sample_args samp;
-             int has_lp; vcla_logprob_args lp; } key;
+             int has_lp; vcla_logprob_args lp; int has_cs; vcla_constrain_args cs; } key;
     memset(&key, 0, sizeof key);
     key.kv_cache = kv_cache; key.key_mask = key_mask; key.ws = ws; key.ctx_max = ctx_max; key.has_samp = sampling != nullptr;
     key.eos_rows = eos_rows; key.rows = rows;
@@ -1482,7 +1498,16 @@ extern "C" int vcla_llama_decode_slots_logprobs(vcla_ctx* ctx, const vcla_slot_a
     if (sampling) memcpy(&key.samp, sampling, sizeof(*sampling));
     key.has_lp = logprobs != nullptr;
     if (logprobs) memcpy(&key.lp, logprobs, sizeof(*logprobs));
+    key.has_cs = constraints != nullptr;
+    if (constraints) memcpy(&key.cs, constraints, sizeof(*constraints));
     return run_steps(ctx->slots_graph, "slots", key, use_graph, n_steps, s, one_step);
+}
+
+extern "C" int vcla_llama_decode_slots_logprobs(vcla_ctx* ctx, const vcla_slot_args* slots, int n_steps, void* kv_cache, int ctx_max,
+                                                const int32_t* key_mask, void* ws, size_t ws_bytes, int use_graph, const vcla_sample_args* sampling,
+                                                const int32_t* eos_rows, const vcla_sample_row* rows, const vcla_logprob_args* logprobs, void* stream) {
+    return vcla_llama_decode_slots_constrained(ctx, slots, n_steps, kv_cache, ctx_max, key_mask, ws, ws_bytes, use_graph, sampling, eos_rows, rows, logprobs,
+                                               nullptr, stream);
 }
 
 extern "C" int vcla_llama_decode_slots_rows(vcla_ctx* ctx, const vcla_slot_args* slots, int n_steps, void* kv_cache, int ctx_max, const int32_t* key_mask,

@@ -292,6 +292,38 @@ def logprob_args(k, token_logprob, top_ids=None, top_logprobs=None, forced=None)
     return a
 
 
+CS_MAX_NODES = 65536        # VCLA_CS_MAX_NODES
+CS_MAX_EDGES = 1 << 20      # VCLA_CS_MAX_EDGES
+CS_MAX_VOCAB = 1 << 19      # VCLA_CS_MAX_VOCAB
+
+
+class CsNode(C.Structure):
+    _fields_ = [("edge0", C.c_int32), ("n_edges", C.c_int32), ("deny", C.c_int32), ("pad", C.c_int32)]
+
+
+class CsEdge(C.Structure):
+    _fields_ = [("token", C.c_int32), ("next", C.c_int32)]
+
+
+class ConstrainArgs(C.Structure):
+    _fields_ = [("nodes", C.c_void_p), ("edges", C.c_void_p), ("state", C.c_void_p), ("n_nodes", C.c_int32), ("n_edges", C.c_int32)]
+
+
+def constrain_args(nodes, edges, state):
+    """vcla_constrain_args over device tensors: nodes int32 [N, 4] (vcla_cs_node), edges int32 [E, 2] (vcla_cs_edge), state int32 [B].  The
+    table is what visualcla/constraints.py built and validated; the struct holds bare pointers: the tensors must stay alive"""
+    for name, x, cols in (("nodes", nodes, 4), ("edges", edges, 2)):
+        if x.dtype != torch.int32 or x.dim() != 2 or x.shape[1] != cols or not x.is_contiguous() or x.shape[0] < 1:
+            raise ValueError(f"constrain_args: {name} must be a contiguous int32 [n >= 1, {cols}] tensor")
+    if state.dtype != torch.int32 or state.dim() != 1 or not state.is_contiguous():
+        raise ValueError("constrain_args: state must be a contiguous int32 [B] tensor")
+    if nodes.shape[0] > CS_MAX_NODES or edges.shape[0] > CS_MAX_EDGES:
+        raise ValueError(f"constrain_args: {nodes.shape[0]} nodes / {edges.shape[0]} edges (caps: VCLA_CS_MAX_NODES = {CS_MAX_NODES}, VCLA_CS_MAX_EDGES = {CS_MAX_EDGES})")
+    a = ConstrainArgs()
+    a.nodes, a.edges, a.state, a.n_nodes, a.n_edges = nodes.data_ptr(), edges.data_ptr(), state.data_ptr(), nodes.shape[0], edges.shape[0]
+    return a
+
+
 # every symbol include/visualcla_hip.h declares: name -> (restype, argtypes)
 _vp, _i, _i64, _f, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
 SYMBOLS = {
@@ -358,6 +390,10 @@ SYMBOLS = {
     "vcla_logprob_scratch_bytes": (_sz, [_i, _i, _i]),
     "vcla_llama_decode_slots_logprobs": (_i, [_vp, C.POINTER(SlotArgs), _i, _vp, _i, _vp, _vp, _sz, _i, C.POINTER(SampleArgs), _vp, _vp,
                                               C.POINTER(LogprobArgs), _vp]),
+    "vcla_constrain_rows": (_i, [_vp, _i64, _i, _i, _vp, C.POINTER(ConstrainArgs), _vp]),
+    "vcla_constrain_advance": (_i, [_vp, _i, _vp, C.POINTER(ConstrainArgs), _vp]),
+    "vcla_llama_decode_slots_constrained": (_i, [_vp, C.POINTER(SlotArgs), _i, _vp, _i, _vp, _vp, _sz, _i, C.POINTER(SampleArgs), _vp, _vp,
+                                                 C.POINTER(LogprobArgs), C.POINTER(ConstrainArgs), _vp]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -595,6 +631,25 @@ def logprob_pick(logits, n_hist_rows, args: LogprobArgs, hist_cap: int, lse, ids
     check(load().vcla_logprob_pick(logits.data_ptr(), logits.stride(0), B, V, n_hist_rows.data_ptr(), int(hist_cap), C.byref(args), lse.data_ptr(),
                                    ids.data_ptr(), stream_ptr()))
     return ids
+
+
+def constrain_rows(logits, n_hist_rows, args: ConstrainArgs) -> None:
+    """vcla_constrain_rows: logits [B, V] fp32 (row stride >= V), masked IN PLACE by the node of every row (args.state int32 [B]); rows whose
+    state or n_hist_rows entry is negative are untouched"""
+    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1:
+        raise ValueError("constrain_rows: logits must be a [B, V] float32 tensor with unit column stride")
+    B, V = logits.shape
+    if n_hist_rows.dtype != torch.int32 or n_hist_rows.numel() != B or not n_hist_rows.is_contiguous():
+        raise ValueError("constrain_rows: n_hist_rows must be int32 [B]")
+    check(load().vcla_constrain_rows(logits.data_ptr(), logits.stride(0), B, V, n_hist_rows.data_ptr(), C.byref(args), stream_ptr()))
+
+
+def constrain_advance(ids, n_hist_rows, args: ConstrainArgs) -> None:
+    """vcla_constrain_advance: ids int64 [B], the tokens taken; args.state moves along the edge taken (an allow node, on a hit)"""
+    B = ids.numel()
+    if ids.dtype != torch.int64 or not ids.is_contiguous() or n_hist_rows.dtype != torch.int32 or n_hist_rows.numel() != B or not n_hist_rows.is_contiguous():
+        raise ValueError("constrain_advance: ids int64 [B] and n_hist_rows int32 [B] are required")
+    check(load().vcla_constrain_advance(ids.data_ptr(), B, n_hist_rows.data_ptr(), C.byref(args), stream_ptr()))
 
 
 def kv_blocks_copy(kv, pool, entries, to_pool: bool) -> None:

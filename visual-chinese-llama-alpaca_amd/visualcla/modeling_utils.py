@@ -168,7 +168,7 @@ def chat(model, image: Union[str, "Image.Image", torch.Tensor], text: str, histo
 
 @torch.inference_mode()
 def chat_many(model, items, generation_config=None, max_batch=64, share_prefix=False, generation_configs=None, seeds=None, prefix_cache=None,
-              logprobs=None):
+              logprobs=None, constraints=None):
     """The bulk form of chat(): items = [(image, text) or (image, text, history), ...] -> [(response, history), ...].  Every prompt is built as
     chat() builds it, the queue is answered by model.generate_many (in-flight batching over max_batch slots) and every response is appended
     to its item's history exactly as chat() appends it.  share_prefix: generate_many's switch -- the system prompt every item begins with and the
@@ -178,9 +178,14 @@ def chat_many(model, items, generation_config=None, max_batch=64, share_prefix=F
     (model.new_prefix_cache(), with share_prefix=True): the system prompt and the image slots survive the call.
     logprobs=k (generate_many's; None: nothing changes): -> [(response, history, output), ...] with output the item's
     RequestOutput(tokens, logprobs, top_ids, top_logprobs) -- the log-probabilities of the RAW distribution, before any processor or
-    warper of the config, one row per generated token.  `target_ids` is not offered here."""
+    warper of the config, one row per generated token.  `target_ids` is not offered here.
+    constraints: an optional list with one entry per item, None or a dict with exactly one of generate_many's request keys
+    `allowed_token_ids`, `banned_token_ids`, `choices` (token ids; string-level choices are not offered), forwarded as that key."""
+    from . import constraints as _constraints
     from .inflight import check_logprobs
     logprobs = check_logprobs(logprobs)
+    if constraints is not None:
+        constraints = _constraints.from_items(constraints, len(items))
     for name, lst in (("generation_configs", generation_configs), ("seeds", seeds)):
         if lst is not None and len(lst) != len(items):
             raise ValueError(f"chat_many: {name} has {len(lst)} entries for {len(items)} items")
@@ -202,6 +207,8 @@ def chat_many(model, items, generation_config=None, max_batch=64, share_prefix=F
                 generation_configs[i].bos_token_id = generation_configs[i].bos_token_id or model.tokenizer.bos_token_id
         if seeds is not None and seeds[i] is not None:
             r["seed"] = seeds[i]
+        if constraints is not None and constraints[i] is not None:
+            r.update(constraints[i])
     outs = model.generate_many(requests, max_batch=max_batch, generation_config=gc, share_prefix=share_prefix,
                                **({} if prefix_cache is None else dict(prefix_cache=prefix_cache)),
                                **({} if logprobs is None else dict(logprobs=logprobs)))

@@ -1224,12 +1224,15 @@ class VisualCLAModel:
 
     def _inflight_request(self, i: int, r, logprobs: Optional[int] = None) -> dict:
         """one entry of generate_many's `requests` -> ids [T] int64, pixel_values [C, H, W] or None, attention_mask [T] or None (on the device);
-        `target` (a host list of ids, or None): the request's target_ids -- only with `logprobs`, never beside max_new_tokens"""
+        `target` (a host list of ids, or None): the request's target_ids -- only with `logprobs`, never beside max_new_tokens;
+        `constraint`: the spec of its allowed_token_ids / banned_token_ids / choices key (visualcla/constraints.py), or None"""
+        from . import constraints
         if not isinstance(r, dict) or r.get("input_ids") is None:
             raise ValueError(f"request {i}: a dict with `input_ids` is required")
-        unknown = set(r) - {"input_ids", "pixel_values", "attention_mask", "max_new_tokens", "generation_config", "seed", "target_ids"}
+        unknown = set(r) - {"input_ids", "pixel_values", "attention_mask", "max_new_tokens", "generation_config", "seed", "target_ids", *constraints.KEYS}
         if unknown:
             raise ValueError(f"request {i}: unknown keys {sorted(unknown)}")
+        constraint = constraints.parse(i, r)                      # host lists: checked before anything moves to the device
 
         def row(x, dims, what):
             if x is None:
@@ -1264,7 +1267,7 @@ class VisualCLAModel:
                 raise ValueError(f"request {i}: target_ids must be a 1-D sequence of at least one integer id (got shape {tuple(tg.shape)}, {tg.dtype})")
             target = [int(x) for x in tg.tolist()]
         return dict(ids=ids, px=row(r.get("pixel_values"), 3, "pixel_values"), am=am, max_new_tokens=mnt, generation_config=rc, seed=seed,
-                    target=target)
+                    target=target, constraint=constraint)
 
     def _request_configs(self, gc, reqs):
         """the resolved generation config of every request -> (configs, class of every request, one config per class).  A request without
@@ -1309,6 +1312,20 @@ class VisualCLAModel:
         return [len(r["target"]) if r.get("target") is not None else int(r["max_new_tokens"]) if r["max_new_tokens"] is not None else
                 new_token_budget(g if (r["generation_config"] is not None and own_budget(r["generation_config"])) else gc, T)
                 for r, g, T in zip(reqs, gcs, lens)]
+
+    @staticmethod
+    def _constraint_table(reqs, gcs, vocab_size: int):
+        """the queue's automaton table (visualcla/constraints.py), None without a constrained request; every refusal that depends on a
+        request's resolved config, by request index.  Needs no device."""
+        from . import constraints
+        from .logits_processors import min_token_floor
+        specs = [r.get("constraint") for r in reqs]
+        if all(sp is None for sp in specs):
+            return None
+        eos_of = [VisualCLAModel._eos_list(g) for g in gcs]
+        for i, (sp, g, eos) in enumerate(zip(specs, gcs, eos_of)):
+            constraints.check(i, sp, vocab_size, eos, min_token_floor(g, 0) if eos else 0, g.no_repeat_ngram_size or 0)
+        return constraints.build(specs, eos_of)
 
     @staticmethod
     def _uses_sampler(gc) -> bool:
@@ -1391,7 +1408,18 @@ class VisualCLAModel:
         target_ids[t] instead of the selected id, its budget is len(target_ids), tokens == target_ids (cut behind the first eos of its
         config), logprobs scores the targets and top_* still describes the model's own distribution at every position.  A forced request
         draws no uniforms.  With logprobs a queue of one request (or max_batch=1) takes the slots route at one slot.
-        last_inflight_stats gains `logprobs` and `forced_requests`."""
+        last_inflight_stats gains `logprobs` and `forced_requests`.
+
+        Constraints as data (visualcla/constraints.py, csrc/constrain.hip): at most one of three request keys, host
+        lists of ints.  `allowed_token_ids=[...]`: every generated token is one of these ids.  `banned_token_ids=[...]`: none of them is
+        ever generated.  `choices=[[ids...], ...]`: the generated tokens, up to the eos, spell exactly one of the sequences -- at step t
+        the next tokens of the choices consistent with what the request generated so far are allowed, at a completed choice every eos id
+        of the request's own config as well (the eos is returned; a budget shorter than the choice cuts it).  result[i] is what generate()
+        returns for request i alone under the equivalent `prefix_allowed_tokens_fn`.  The queue becomes one automaton table in device
+        memory; the captured step masks the row the selector reads and moves every slot's state, without returning to the host.
+        `logprobs` stay RAW: they do not see the constraint.  Not beside `target_ids`; `choices` needs an eos_token_id and excludes
+        no_repeat_ngram_size and a min-token floor.  A queue of one constrained request (or max_batch=1) takes the slots route at one
+        slot.  last_inflight_stats gains `constrained_requests`, `automaton_nodes`, `automaton_edges`."""
         from .inflight import InflightScheduler, RequestOutput, check_logprobs
         from .prefix_cache import PrefixCache
         logprobs = check_logprobs(logprobs)                       # before anything else: the argument by name
@@ -1438,15 +1466,18 @@ class VisualCLAModel:
                            seeded=sum(sd is not None for sd in seeds))
         if logprobs is not None:
             extra_stats.update(logprobs=logprobs, forced_requests=sum(tg is not None for tg in targets))
+        ctable = self._constraint_table(reqs, gcs, t["vocab_size"])      # refusals by request index, and the caps, before any kernel runs
+        if ctable is not None:
+            extra_stats.update(ctable.stats())
         # raises for a prompt that leaves no room, by index, before any kernel runs
         sched = InflightScheduler(lens, budgets, [r["px"] is not None for r in reqs], max_batch, t["max_position_embeddings"], self.image_at_head,
                                   steps_per_sync, share_prefix=bool(share_prefix), logprobs=logprobs, targets=targets)
         if use_graph is None:
             use_graph = os.environ.get("VCLA_DECODE_GRAPH", "1") != "0"
-        if sched.slots == 1 and ((prefix_cache is None and logprobs is None) or not reqs):
+        if sched.slots == 1 and ((prefix_cache is None and logprobs is None and ctable is None) or not reqs):
             # max_batch = 1 or a single request: generate() per request (the persistent B = 1 step is the fast path there).  With a prefix
             # cache such a queue stays on the slots route, at one slot: generate() has no place for cached rows; with logprobs too: the
-            # persistent B = 1 step folds its greedy tail and produces no logits
+            # persistent B = 1 step folds its greedy tail and produces no logits; with a constrained request for the same reason
             out = []
             for i, r in enumerate(reqs):
                 self._request_seed = seeds[i]                     # the private hook _draw_uniforms reads: no public argument of generate()
@@ -1482,7 +1513,7 @@ class VisualCLAModel:
             side.wait_stream(cur_stream)
         with torch.cuda.device(self._device), torch.cuda.stream(side if side is not None else cur_stream):
             try:
-                out = slots_run.SlotsRun(self, class_gcs[0], reqs, sched, bool(use_graph), plan, gcs if len(class_gcs) > 1 else None, seeds, pstate, logprobs).run()
+                out = slots_run.SlotsRun(self, class_gcs[0], reqs, sched, bool(use_graph), plan, gcs if len(class_gcs) > 1 else None, seeds, pstate, logprobs, ctable).run()
             except BaseException:
                 if pstate is not None:                            # the index may name blocks whose copies were never enqueued
                     prefix_cache.end()

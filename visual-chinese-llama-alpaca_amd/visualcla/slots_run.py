@@ -1,5 +1,5 @@
 """The slots loop of VisualCLAModel.generate_many (DESIGN.md sections 7c-7h): one SlotsRun per call holds the buffers, the scheduler and
-what the features switched on add -- PerRequest (per-slot eos lists and sampler records, 7f), Logprobs (7h), PrefixShare (7e, 7g); None
+what the features switched on add -- PerRequest (per-slot eos lists and sampler records, 7f), Logprobs (7h), Constraints (7i), PrefixShare (7e, 7g); None
 where the feature is off -- and admits, steps and harvests until the queue is empty.  The model (`self.m`) keeps its kernels' wrappers."""
 from __future__ import annotations
 
@@ -30,6 +30,15 @@ class Logprobs:
 
     def __init__(self, k: int, lp: torch.Tensor, top_ids: Optional[torch.Tensor], top_lp: Optional[torch.Tensor], forced: Optional[torch.Tensor], args):
         self.k, self.lp, self.top_ids, self.top_lp, self.forced, self.first, self.args = k, lp, top_ids, top_lp, forced, {}, args
+
+
+class Constraints:
+    """a queue with constrained requests: the table of visualcla/constraints.py (roots[i]: request i's root node, -1 = unconstrained), its
+    two device tensors, state int32 [B] (the node of every slot) and the step's vcla_constrain_args over them"""
+    __slots__ = ("table", "nodes", "edges", "state", "args")
+
+    def __init__(self, table, nodes: torch.Tensor, edges: torch.Tensor, state: torch.Tensor):
+        self.table, self.nodes, self.edges, self.state, self.args = table, nodes, edges, state, _lib.constrain_args(nodes, edges, state)
 
 
 class PrefixShare:
@@ -129,9 +138,10 @@ def cut_calls(rows_of, members, max_rows: int, alone_above: int) -> List[List[in
 class SlotsRun:
     """gcs None: one config `gc` for the whole queue.  Else gcs[i] is request i's config, there are at least two distinct ones, and the
     step reads per-slot tables (_per_request_tables).  pstate: the call's state of a prefix cache (PrefixCache.begin), or None.
-    logprobs (k or None): the step also runs the stats pass and the pick (csrc/logprobs.hip); sched.targets[i] forces request i."""
+    logprobs (k or None): the step also runs the stats pass and the pick (csrc/logprobs.hip); sched.targets[i] forces request i.
+    constraints (a constraints.Table or None): the step also runs the mask and the transition (csrc/constrain.hip)."""
 
-    def __init__(self, model, gc, reqs, sched, use_graph, plan=None, gcs=None, seeds=None, pstate=None, logprobs=None):
+    def __init__(self, model, gc, reqs, sched, use_graph, plan=None, gcs=None, seeds=None, pstate=None, logprobs=None, constraints=None):
         self.m, self.reqs, self.sched, self.use_graph, self.dev = model, reqs, sched, use_graph, model._device
         self.lib = lib = _lib.load()
         t, B, ctx_max, cap, W = model.config.text_config, sched.slots, sched.ctx_max, sched.cap, _lib.SLOT_SUMMARY_WORDS
@@ -162,13 +172,16 @@ class SlotsRun:
         ws_bytes = lib.vcla_llama_workspace_bytes(model._ctx, B, 1)
         if logprobs is not None:
             k = int(logprobs)
-            ws_bytes += lib.vcla_logprob_scratch_bytes(B, t["vocab_size"], int(samp_kw is not None))
+            ws_bytes += lib.vcla_logprob_scratch_bytes(B, t["vocab_size"], int(samp_kw is not None or constraints is not None))
             bufs = (model._typed_buf("if_lp", (cap, B), torch.float32),
                     model._typed_buf("if_top_ids", (cap, B, k), torch.int64) if k else None,
                     model._typed_buf("if_top_lp", (cap, B, k), torch.float32) if k else None,
                     model._typed_buf("if_forced", (cap, B), torch.int64).fill_(-1) if any(tg is not None for tg in sched.targets) else None)
             self.lp = Logprobs(k, *bufs, _lib.logprob_args(k, *bufs))
         self.ws = model._buf("slots", ws_bytes)
+        self.cons = None
+        if constraints is not None:                             # the table is uploaded once; every slot starts unconstrained
+            self.cons = Constraints(constraints, *constraints.tensors(self.dev), model._typed_buf("if_cs_state", (B,), torch.int32).fill_(-1))
         self.slot_args = _lib.slot_args(eos, row_pos, count, budget, hist_len, hist, cur, summary)
         self.samp = _lib.sample_args(uniforms=uni, history=hist, **samp_kw) if samp_kw is not None else None
         self.count_h, self.share = [0] * B, None
@@ -186,6 +199,8 @@ class SlotsRun:
                     self.draw_uniforms(groups)
                 if self.lp is not None and self.lp.forced is not None:
                     self.fill_forced(groups)
+                if self.cons is not None:
+                    self.fill_state(groups)
                 for g in groups:
                     if self.per is not None:
                         self.fill_rows(g.requests, g.slots)
@@ -223,6 +238,11 @@ class SlotsRun:
                 if sched.targets[i] is not None:
                     forced[:sched.budget[i], b] = torch.tensor(sched.targets[i], dtype=torch.int64, device=self.dev)
 
+    def fill_state(self, groups) -> None:
+        """the automaton state of every slot that is filled: the request's root node, -1 = unconstrained (first_token then moves it)"""
+        pairs = [(b, self.cons.table.roots[i]) for g in groups for i, b in zip(g.requests, g.slots)]
+        self.cons.state[torch.tensor([b for b, _ in pairs], device=self.dev)] = torch.tensor([r for _, r in pairs], dtype=torch.int32, device=self.dev)
+
     def fill_rows(self, requests, slots) -> None:
         """admission: the table rows of the slots it fills, rewritten between two chunks of steps"""
         per = self.per
@@ -234,8 +254,21 @@ class SlotsRun:
     def first_token(self, logits, requests, sl):
         """the first token of the requests whose prefill produced `logits` (row j = requests[j], slot sl[j]): the same selector as the steps,
         at history length 0 -- argmax, the uniform sampler, or the table entry with the admitted requests' own records.  logprobs: the stats pass over
-        the raw logits before it (a sampler then works on the copy), the pick with the requests' forced[0] behind it; into row 0 of the slots' columns and lp.first"""
-        per, lp, dev, G = self.per, self.lp, self.dev, len(requests)
+        the raw logits before it (a sampler then works on the copy), the pick with the requests' forced[0] behind it; into row 0 of the slots' columns and lp.first.
+        constraints: the mask on the row the selector reads and the transition behind it, on a compact state of the admitted requests' roots;
+        the moved states go into the slots' entries"""
+        per, lp, cons, dev, G = self.per, self.lp, self.cons, self.dev, len(requests)
+        c_state = c_args = None
+        if cons is not None and any(cons.table.roots[i] >= 0 for i in requests):
+            c_state = torch.tensor([cons.table.roots[i] for i in requests], dtype=torch.int32, device=dev)
+            c_args = _lib.constrain_args(cons.nodes, cons.edges, c_state)
+        zeros = torch.zeros(G, dtype=torch.int32, device=dev) if lp is not None or c_args is not None else None
+
+        def advance(ids):
+            if c_args is not None:
+                _lib.constrain_advance(ids, zeros, c_args)
+                cons.state[sl] = c_state
+            return ids
 
         def select(x):                                          # (`x` is modified by a sampler)
             u0 = self.uni[0, sl].view(1, G).contiguous() if self.uni is not None else None
@@ -246,18 +279,22 @@ class SlotsRun:
                 return _lib.argmax(x)
             return _lib.sample(x, _lib.sample_args(uniforms=u0, **self.samp_kw), n_hist=0)
         if lp is None:
-            return select(logits)
+            if c_args is not None:
+                _lib.constrain_rows(logits, zeros, c_args)      # in place on the admission logits
+            return advance(select(logits))
         k = lp.k
-        zeros = torch.zeros(G, dtype=torch.int32, device=dev)
         t_lp = torch.empty(1, G, dtype=torch.float32, device=dev)
         t_ids = torch.empty(1, G, k, dtype=torch.int64, device=dev) if k else None
         t_top = torch.empty(1, G, k, dtype=torch.float32, device=dev) if k else None
         f0 = lp.forced[0, sl].view(1, G).contiguous() if lp.forced is not None else None
         args = _lib.logprob_args(k, t_lp, t_ids, t_top, f0)
-        work = torch.empty_like(logits) if self.samp_kw is not None else None     # the sampler modifies its input; the gather needs the raw rows
+        work = torch.empty_like(logits) if self.samp_kw is not None or c_args is not None else None     # the sampler and the mask modify their input; the gather needs the raw rows
         lse = _lib.logprob_rows(logits, zeros, args, 1, copy=work)
+        if c_args is not None:
+            _lib.constrain_rows(work, zeros, c_args)
         first = select(logits if work is None else work)
         _lib.logprob_pick(logits, zeros, args, 1, lse, first)
+        advance(first)
         lp.lp[0, sl] = t_lp[0]
         if k:
             lp.top_ids[0, sl] = t_ids[0]
@@ -389,12 +426,13 @@ class SlotsRun:
         self.start_slots(g.requests, g.slots, [first_of[i] for i in g.requests], plan.T)      # every slot decodes from its own T
 
     def decode_chunk(self, n: int) -> None:
-        """n steps of every live slot, one call; the per-slot tables and the logprob block are null where the feature is off"""
+        """n steps of every live slot, one call; the per-slot tables, the logprob block and the constraints are null where the feature is off"""
         per, ws = self.per, self.ws
-        _lib.check(self.lib.vcla_llama_decode_slots_logprobs(
+        _lib.check(self.lib.vcla_llama_decode_slots_constrained(
             self.m._ctx, C.byref(self.slot_args), n, self.kv.data_ptr(), self.sched.ctx_max, self.km.data_ptr(), ws.data_ptr(), ws.numel(),
             int(self.use_graph), C.byref(self.samp) if self.samp is not None else None, per.eos_dev.data_ptr() if per is not None else None,
-            _lib.ptr(per.rows_dev) if per is not None else None, C.byref(self.lp.args) if self.lp is not None else None, _lib.stream_ptr()))
+            _lib.ptr(per.rows_dev) if per is not None else None, C.byref(self.lp.args) if self.lp is not None else None,
+            C.byref(self.cons.args) if self.cons is not None else None, _lib.stream_ptr()))
 
     def harvest(self, host) -> None:
         """`host`: the slot table after a chunk.  The finished slots' columns of the history and of the logprob buffers go to the scheduler"""
