@@ -791,6 +791,13 @@ int vcla_llama_decode_slots_constrained(vcla_ctx* ctx, const vcla_slot_args* slo
                                         const int32_t* eos_rows, const vcla_sample_row* rows, const vcla_logprob_args* logprobs,
                                         const vcla_constrain_args* constraints, void* stream);
 
+/* ---------------------------------------------------------------- debug */
+/* The label of the calling thread's most recent kernel launch through this library ("" before the first): a string literal that
+   names the kernel and, for the attention dispatchers (vcla_attention, vcla_attn_decode_*, vcla_attn_verify, the persistent decode
+   step), the template instantiation selected, e.g. "attn_mfma_kernel<128, 4, 2>".  For tests that must know which kernel their
+   call ran; the labels are not part of the ABI contract.  A launch replayed from a hipGraph does not update it. */
+const char* vcla_debug_last_launch(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,40 +27,70 @@ def small7b():
     torch.cuda.empty_cache()
 
 
+class _Prefilled:
+    """a T-token prompt prefilled once (VCLA_ENGINE = mode), and host-driven decode steps (vcla_llama_decode_step) on its cache"""
+
+    def __init__(self, m, T, masked, ctx_max=None, mode="0"):
+        from visualcla import _lib
+        self.m, self.T, self.L, self.lib = m, T, _lib, _lib.load()
+        dev = m.device
+        self.V = m.config.text_config["vocab_size"]
+        ids = torch.randint(3, self.V - 8, (1, T), generator=torch.Generator().manual_seed(5)).to(dev)
+        self.ctx_max = ctx_max or (T + 8 + 63) // 64 * 64
+        embeds, _ = m._embed(ids, None, None)
+        self.cache = m._new_cache(1, self.ctx_max)
+        self.cache.kv.zero_()
+        am = None
+        if masked:                     # holes in the prompt's mask: the MASK instantiation must skip exactly those keys
+            am = torch.ones(1, T, dtype=torch.int64, device=dev)
+            am[0, 3:9] = 0
+            am[0, T // 2] = 0
+        self.key_mask = m._key_mask(am, 1, T, self.ctx_max)
+        os.environ["VCLA_ENGINE"] = mode
+        logits = m._prefill(embeds, self.cache, self.key_mask, all_logits=False)
+        self.ws = m._buf("llama", self.lib.vcla_llama_workspace_bytes(m._ctx, 1, 1))
+        self.tok = logits.argmax(-1).contiguous()
+        torch.cuda.synchronize()
+        self.kv0 = self.cache.kv.clone()
+
+    def step(self, mode, pos, tok):
+        """one host-driven decode step at `pos` on the cache as it stands -> (logits, the label of the step's last launch)"""
+        os.environ["VCLA_ENGINE"] = mode
+        out = torch.empty(1, self.V, dtype=torch.float32, device=self.m.device)
+        self.L.check(self.lib.vcla_llama_decode_step(self.m._ctx, tok.data_ptr(), 1, pos, None, 0, self.cache.kv.data_ptr(), self.ctx_max, self.L.ptr(self.key_mask),
+                                                     out.data_ptr(), None, self.ws.data_ptr(), self.ws.numel(), self.L.stream_ptr()))
+        label = self.L.last_launch()
+        self.L.check(self.lib.vcla_llama_decode_status(self.m._ctx, 1, self.ws.data_ptr(), self.ws.numel(), self.L.stream_ptr()))
+        torch.cuda.synchronize()
+        return out, label
+
+    def planted_step(self, mode, rows, c, second=None):
+        """restore the cache, (second: run the step at T first, with the token `second` for the step at T + 1), plant `rows` of the last layer, step"""
+        self.cache.kv.copy_(self.kv0)
+        pos, tok = self.T, self.tok
+        if second is not None:
+            self.step(mode, pos, tok)
+            pos, tok = pos + 1, second
+        last = self.kv0.shape[0] - 1
+        for j in rows:
+            self.cache.kv[last, 0, 0, :, j] = 0.0
+            self.cache.kv[last, 1, 0, :, j] = c
+        return self.step(mode, pos, tok)
+
+
 def _steps(m, mode, T, n_steps, masked, forced=None):
     """prefill a T-token prompt, then n_steps host-driven decode steps (vcla_llama_decode_step) with VCLA_ENGINE = mode; returns tokens, logits, cache"""
-    from visualcla import _lib
-    lib = _lib.load()
-    os.environ["VCLA_ENGINE"] = mode
-    dev = m.device
-    V = m.config.text_config["vocab_size"]
-    ids = torch.randint(3, V - 8, (1, T), generator=torch.Generator().manual_seed(5)).to(dev)
-    ctx_max = (T + n_steps + 2 + 63) // 64 * 64
-    embeds, _ = m._embed(ids, None, None)
-    cache = m._new_cache(1, ctx_max)
-    cache.kv.zero_()
-    am = None
-    if masked:                     # holes in the prompt's mask: the MASK instantiation must skip exactly those keys
-        am = torch.ones(1, T, dtype=torch.int64, device=dev)
-        am[0, 3:9] = 0
-        am[0, T // 2] = 0
-    key_mask = m._key_mask(am, 1, T, ctx_max)
-    logits = m._prefill(embeds, cache, key_mask, all_logits=False)
-    ws = m._buf("llama", lib.vcla_llama_workspace_bytes(m._ctx, 1, 1))
-    step_logits = torch.empty(1, V, dtype=torch.float32, device=dev)
-    tok = logits.argmax(-1)
+    p = _Prefilled(m, T, masked, ctx_max=(T + n_steps + 2 + 63) // 64 * 64, mode=mode)
+    tok = p.tok
     toks, lgs = [int(tok)], []
     for s in range(n_steps):
         if forced is not None:
-            tok = torch.tensor([forced[s]], device=dev)
-        _lib.check(lib.vcla_llama_decode_step(m._ctx, tok.contiguous().data_ptr(), 1, T + s, None, 0, cache.kv.data_ptr(), ctx_max, _lib.ptr(key_mask),
-                                              step_logits.data_ptr(), None, ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
-        _lib.check(lib.vcla_llama_decode_status(m._ctx, 1, ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
-        lgs.append(step_logits.clone())
+            tok = torch.tensor([forced[s]], device=m.device)
+        step_logits, _ = p.step(mode, T + s, tok.contiguous())
+        lgs.append(step_logits)
         tok = step_logits.argmax(-1)
         toks.append(int(tok))
-    torch.cuda.synchronize()
-    return toks, lgs, cache.kv[..., :T + n_steps, :].float().clone()
+    return toks, lgs, p.cache.kv[..., :T + n_steps, :].float().clone()
 
 
 # 510 / 509: the four steps cross args.split_min = 512 inside one loop (one CU per head -> the head's 8 CUs share the cache walk); 1011 / 700 / 1900: split throughout
@@ -219,3 +249,67 @@ def test_split_attention_equals_the_one_cu_walk(small7b):
             d = (got["0"][1][s] - got["128"][1][s]).abs()
             assert d.max().item() < 0.06 and d.mean().item() < 0.01, (T, s, d.max().item(), d.mean().item())
         assert (got["0"][2] - got["128"][2]).abs().max().item() < 0.05          # the appended K / V rows
+
+
+# ------------------------------------------------------------------ a key that matters in the last layer's cache (tests/attention_probe.py)
+# At 700 / 1900 keys a key lost by the engine's attention moves the logits by less than the 0.2 / 0.04 the two forms may differ by.  Here one cache row
+# of the LAST layer gets K = 0 and the value PLANT_C in every head: the smallest power of two for which the LAUNCH path's logits move by mean |d| >= 0.2
+# (5 x the mean bound) from its own unplanted step -- chosen by measurement on the launch path alone and asserted below as a precondition
+# for every plant below, with and without the mask (profiles/attention_seams.txt records the measured moves; T = 700: 1024 gives 0.201 unmasked but
+# 0.189 masked).
+PLANT_C = {300: 512.0, 700: 2048.0, 1900: 4096.0}
+
+
+def engine_plant_rows(T, masked, split):
+    """one j in every CU's share of a head's keys (j mod 96 = 0, 12, .., 84, and the share ends 11 / 95), both sides of the batch seam, T - 1"""
+    js = [192 + r for r in (0, 12, 24, 36, 48, 60, 72, 84, 11, 95)]
+    seam = 576 if split else (72 if masked else 96)
+    js += [seam - 1, seam, T - 1]
+    if masked:
+        js = [j for j in js if not (3 <= j < 9 or j == T // 2)]
+    return js
+
+
+@pytest.mark.parametrize("T,masked", [(300, False), (300, True), (700, False), (700, True), (1900, False), (1900, True)])
+def test_engine_sees_a_planted_key(small7b, T, masked):
+    """T = 300: one CU walks a head's cache; 700 / 1900: the head's 8 CUs share the walk by j mod 96 and the owner merges (o, m, l).  With the plant in
+    place the engine stays within the existing 0.2 / 0.04 of the launch path, AND its own logits move from its unplanted step by at least half the launch
+    path's move (>= 0.2 mean, the precondition): a lost plant cannot hide inside the bound.  The step's own position: two steps, the plant on the row the
+    first one appended.  Under a zero of the mask, and in the stale rows T + 1 .. T + 3, the plant leaves the engine's logits bit-identical."""
+    p = _Prefilled(small7b, T, masked)
+    c = PLANT_C[T]
+    split = T >= 512
+    label = f"decode_engine_kernel<MASK={'true' if masked else 'false'},SPLITK={'true' if split else 'false'}>"
+    try:
+        base0, label0 = p.planted_step("0", (), c)
+        base1, got_label = p.planted_step("1", (), c)
+        assert got_label == label, got_label
+        assert not label0.startswith("decode_engine_kernel"), f"the reference step ran the engine ({label0})"
+        tok2 = base0.argmax(-1).contiguous()
+        base0b, _ = p.planted_step("0", (), c, second=tok2)
+        base1b, _ = p.planted_step("1", (), c, second=tok2)
+        moves = []
+        for j in engine_plant_rows(T, masked, split) + [T]:
+            second = tok2 if j == T else None
+            b0, b1 = (base0b, base1b) if j == T else (base0, base1)
+            l0, _ = p.planted_step("0", (j,), c, second=second)
+            l1, _ = p.planted_step("1", (j,), c, second=second)
+            move0, move1 = (l0 - b0).abs().mean().item(), (l1 - b1).abs().mean().item()
+            d = (l0 - l1).abs()
+            print(f"[attention_seams] engine T={T} masked={int(masked)} j={j} c={c}: launch path moved {move0:.3f}, engine moved {move1:.3f}, "
+                  f"engine vs launch max {d.max().item():.3f} mean {d.mean().item():.4f}")
+            moves.append(move0)
+            assert torch.isfinite(l1).all()
+            assert move0 >= 0.2, f"precondition: the plant at {j} moves the launch path's logits by only {move0:.3f} (c = {c})"
+            assert d.max().item() <= 0.2 and d.mean().item() <= 0.04, (T, j, d.max().item(), d.mean().item())
+            assert move1 >= 0.5 * move0, f"the engine's logits moved {move1:.3f} with the plant at {j}, the launch path's {move0:.3f}"
+        if masked:
+            for rows in ((5,), (T // 2,), (T + 1, T + 2, T + 3)):
+                l1, _ = p.planted_step("1", rows, c)
+                assert torch.equal(l1, base1), f"rows {rows} must be invisible to the engine"
+        else:
+            l1, _ = p.planted_step("1", (T + 1, T + 2, T + 3), c)
+            assert torch.equal(l1, base1), "the stale rows past the position must be invisible to the engine"
+        print(f"[attention_seams] engine T={T} masked={int(masked)} c={c}: launch-path move min {min(moves):.3f} max {max(moves):.3f}")
+    finally:
+        os.environ.pop("VCLA_ENGINE", None)

@@ -833,7 +833,8 @@ def test_fp8_cache_writers_saturate(lib):
     (2, 3, 257, 257, 64, False), (1, 2, 64, 321, 64, False), (2, 4, 48, 48, 128, True), (1, 2, 130, 130, 128, True),
     (1, 2, 128, 128, 128, True), (2, 2, 100, 228, 128, True), (1, 1, 16, 16, 64, False), (1, 2, 577, 577, 64, False),
     (1, 1, 300, 1000, 128, True),
-    # bidirectional d = 64: 2 / 4 / 9 waves per workgroup by sequence length (attention_mfma.hip)
+    # bidirectional d = 64: 2 / 4 waves per workgroup by sequence length (attention_mfma.hip).  The 9-wave form also needs B * H >= 256 and the
+    # whole-prompt d = 128 form B * H * blocks >= 512: no shape here reaches either -- tests/test_gpu_attention_seams.py does, and asserts the label
     (3, 2, 129, 129, 64, False), (1, 1, 288, 288, 64, False), (2, 2, 100, 100, 64, False), (1, 2, 289, 200, 64, False), (2, 1, 33, 64, 64, False),
 ])
 def test_attention_mfma(lib, B, H, Tq, Tk, D, causal):

@@ -26,6 +26,8 @@ def test_library_exports_every_declared_symbol():
     for name in declared:
         assert hasattr(lib, name), name
     assert lib.vcla_version() == 5
+    # the debug hook (additive, ABI version unchanged): a C string, the label of this thread's last launch ("" before the first)
+    assert "vcla_debug_last_launch" in declared and isinstance(_lib.last_launch(), str)
 
 
 def test_no_gpu_fails_loudly():

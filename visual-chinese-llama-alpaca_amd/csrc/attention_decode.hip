@@ -642,24 +642,35 @@ static int launch_decode(const void* qkv, void* kc, void* vc, const float* cos_t
     VCLA_REQUIRE(lds <= 64 * 1024, VCLA_ERR_BAD_SHAPE, "attn_decode: ctx_max=%d needs %zu B of LDS (max 64 KiB)", ctx_max, lds);
     dim3 grid(H, B);
     const int out_frag_mt = out_frag ? (B + 15) / 16 : 0;
+    // the label of the launch names the instantiation (vcla_debug_last_launch): literals picked by D, nothing formatted at run time
+    const char* label = "";
+#define DEC_LBL(pre_, post_) (D == 128 ? pre_ "128" post_ : D == 64 ? pre_ "64" post_ : pre_ "32" post_)
     if constexpr (sizeof(T) == 2) {
         // bf16: the single-pass kernel (the phased kernel below serves fp32 and the outputs it cannot store).  2-wave workgroups once
         // B * H fills the chip that way (16 per CU by waves), 4 waves otherwise; the row-major output needs 16-byte rows.
         const bool flash_ok = out_frag || (((int64_t)H * D) % 8 == 0 && vcla_aligned(out, 16));
         const bool small_wg = (int64_t)B * H >= 1024;
 #define FD_GO(NW_, MASK_, KV8_) FD_GOR(NW_, MASK_, KV8_, false)
-#define FD_GOR(NW_, MASK_, KV8_, ROWS_) attn_decode_flash_kernel<D, NW_, MASK_, KV8_, false, ROWS_><<<grid, NW_ * 64, 0, s>>>(qkv, kc, vc, cos_tab, sin_tab, \
-                                                    (bf16_t*)out, H, ctx_max, pos0, pos_dev, key_mask, key_mask_ld, scale, out_frag_mt)
+#define FD_GOR(NW_, MASK_, KV8_, ROWS_)                                                                                                                      \
+    do {                                                                                                                                                    \
+        attn_decode_flash_kernel<D, NW_, MASK_, KV8_, false, ROWS_><<<grid, NW_ * 64, 0, s>>>(qkv, kc, vc, cos_tab, sin_tab, (bf16_t*)out, H, ctx_max, pos0, \
+                                                                                              pos_dev, key_mask, key_mask_ld, scale, out_frag_mt);          \
+        label = DEC_LBL("attn_decode_flash_kernel<D=", ",NW=" #NW_ ",MASK=" #MASK_ ",KV8=" #KV8_ ",QP=false,ROWS=" #ROWS_ ">");                             \
+    } while (0)
         VCLA_REQUIRE(!rows || (!qp && !kv8), VCLA_ERR_BAD_ARG, "attn_decode: per-row positions go with the bf16 cache and the plain qkv row");
         if (qp) {    // q / k / v arrive as two raw fp32 K slices of the qkv projection: 2-wave form only (batch decode, B * H >= 1024)
             if constexpr (D >= 64) {
                 VCLA_REQUIRE(flash_ok && small_wg, VCLA_ERR_BAD_ARG, "attn_decode: the split-qkv form needs B * H >= 1024 and a 16-byte aligned output");
-#define FD_GOP(MASK_, KV8_) attn_decode_flash_kernel<D, 2, MASK_, KV8_, true><<<grid, 128, 0, s>>>(qkv, kc, vc, cos_tab, sin_tab, (bf16_t*)out, H, ctx_max, pos0, pos_dev, \
-                                                                                                 key_mask, key_mask_ld, scale, out_frag_mt, *qp)
+#define FD_GOP(MASK_, KV8_)                                                                                                                                  \
+    do {                                                                                                                                                    \
+        attn_decode_flash_kernel<D, 2, MASK_, KV8_, true><<<grid, 128, 0, s>>>(qkv, kc, vc, cos_tab, sin_tab, (bf16_t*)out, H, ctx_max, pos0, pos_dev,       \
+                                                                               key_mask, key_mask_ld, scale, out_frag_mt, *qp);                             \
+        label = DEC_LBL("attn_decode_flash_kernel<D=", ",NW=2,MASK=" #MASK_ ",KV8=" #KV8_ ",QP=true,ROWS=false>");                                          \
+    } while (0)
                 if (kv8) { if (key_mask) FD_GOP(true, true); else FD_GOP(false, true); }
                 else { if (key_mask) FD_GOP(true, false); else FD_GOP(false, false); }
 #undef FD_GOP
-                VCLA_CHECK_LAUNCH("attn_decode_flash_kernel<split qkv>");
+                VCLA_CHECK_LAUNCH(label);
                 return VCLA_OK;
             } else {
                 return vcla_fail(VCLA_ERR_BAD_SHAPE, "attn_decode: the split-qkv form needs head dim 64 or 128 (got %d)", D);
@@ -670,7 +681,7 @@ static int launch_decode(const void* qkv, void* kc, void* vc, const float* cos_t
                 VCLA_REQUIRE(flash_ok, VCLA_ERR_BAD_ARG, "attn_decode: the fp8 cache needs a 16-byte aligned output with H * d %% 8 == 0");
                 if (small_wg) { if (key_mask) FD_GO(2, true, true); else FD_GO(2, false, true); }
                 else { if (key_mask) FD_GO(4, true, true); else FD_GO(4, false, true); }
-                VCLA_CHECK_LAUNCH("attn_decode_flash_kernel<fp8 cache>");
+                VCLA_CHECK_LAUNCH(label);
                 return VCLA_OK;
             } else {
                 return vcla_fail(VCLA_ERR_BAD_SHAPE, "attn_decode: the fp8 cache needs head dim 64 or 128 (got %d)", D);
@@ -679,39 +690,38 @@ static int launch_decode(const void* qkv, void* kc, void* vc, const float* cos_t
         if (flash_ok && rows) {
             if (small_wg) { if (key_mask) FD_GOR(2, true, false, true); else FD_GOR(2, false, false, true); }
             else { if (key_mask) FD_GOR(4, true, false, true); else FD_GOR(4, false, false, true); }
-            VCLA_CHECK_LAUNCH("attn_decode_flash_kernel<rows>");
+            VCLA_CHECK_LAUNCH(label);
             return VCLA_OK;
         }
         if (flash_ok) {
             if (small_wg) { if (key_mask) FD_GO(2, true, false); else FD_GO(2, false, false); }
             else { if (key_mask) FD_GO(4, true, false); else FD_GO(4, false, false); }
-            VCLA_CHECK_LAUNCH("attn_decode_flash_kernel");
+            VCLA_CHECK_LAUNCH(label);
             return VCLA_OK;
         }
 #undef FD_GO
 #undef FD_GOR
     }
     const bool coop = (int64_t)B * H >= 512;
+#define PD_GO(COOP_, NW_, ROWS_)                                                                                                                            \
+    do {                                                                                                                                                    \
+        attn_decode_kernel<T, D, COOP_, NW_, ROWS_><<<grid, NW_ * 64, lds, s>>>((const T*)qkv, (T*)kc, (T*)vc, cos_tab, sin_tab, (T*)out, H, ctx_max, pos0,  \
+                                                                                pos_dev, key_mask, key_mask_ld, scale, sc_cap, out_frag_mt);                \
+        label = sizeof(T) == 2 ? DEC_LBL("attn_decode_kernel<bf16,D=", ",COOP=" #COOP_ ",NW=" #NW_ ",ROWS=" #ROWS_ ">")                                     \
+                               : DEC_LBL("attn_decode_kernel<f32,D=", ",COOP=" #COOP_ ",NW=" #NW_ ",ROWS=" #ROWS_ ">");                                      \
+    } while (0)
     if (rows) {
-#define PD_GOR(COOP_, NW_) attn_decode_kernel<T, D, COOP_, NW_, true><<<grid, NW_ * 64, lds, s>>>((const T*)qkv, (T*)kc, (T*)vc, cos_tab, sin_tab, (T*)out, H, ctx_max, \
-                                                                                              pos0, pos_dev, key_mask, key_mask_ld, scale, sc_cap, out_frag_mt)
-        if (coop && NWs == 2) PD_GOR(true, 2);
-        else if (coop) PD_GOR(true, 4);
-        else PD_GOR(false, 4);
-#undef PD_GOR
-        VCLA_CHECK_LAUNCH("attn_decode_kernel<rows>");
-        return VCLA_OK;
+        if (coop && NWs == 2) PD_GO(true, 2, true);
+        else if (coop) PD_GO(true, 4, true);
+        else PD_GO(false, 4, true);
+    } else {
+        if (coop && NWs == 2) PD_GO(true, 2, false);
+        else if (coop) PD_GO(true, 4, false);
+        else PD_GO(false, 4, false);
     }
-    if (coop && NWs == 2)
-        attn_decode_kernel<T, D, true, 2><<<grid, 128, lds, s>>>((const T*)qkv, (T*)kc, (T*)vc, cos_tab, sin_tab, (T*)out, H, ctx_max, pos0,
-                                                                 pos_dev, key_mask, key_mask_ld, scale, sc_cap, out_frag_mt);
-    else if (coop)
-        attn_decode_kernel<T, D, true><<<grid, 256, lds, s>>>((const T*)qkv, (T*)kc, (T*)vc, cos_tab, sin_tab, (T*)out, H, ctx_max, pos0,
-                                                              pos_dev, key_mask, key_mask_ld, scale, sc_cap, out_frag_mt);
-    else
-        attn_decode_kernel<T, D, false><<<grid, 256, lds, s>>>((const T*)qkv, (T*)kc, (T*)vc, cos_tab, sin_tab, (T*)out, H, ctx_max, pos0,
-                                                               pos_dev, key_mask, key_mask_ld, scale, sc_cap, out_frag_mt);
-    VCLA_CHECK_LAUNCH("attn_decode_kernel");
+#undef PD_GO
+#undef DEC_LBL
+    VCLA_CHECK_LAUNCH(label);
     return VCLA_OK;
 }
 

@@ -1220,7 +1220,7 @@ int vcla_attention_vit(const vcla_attn_args* a, void* stream) {
         const int rc_ = vcla_raise_dyn_lds((const void*)kern, lds, attr_long);
         if (rc_) return rc_;
         kern<<<grid, 512, lds, s>>>(*a);
-        VCLA_CHECK_LAUNCH("attn_vit_long_kernel");
+        VCLA_CHECK_LAUNCH("attn_vit_long_kernel<9>");
         return VCLA_OK;
     }
 #define VIT_GO(NWM_)                                                                                                 \
@@ -1230,7 +1230,9 @@ int vcla_attention_vit(const vcla_attn_args* a, void* stream) {
         static bool attr_set[VCLA_MAX_DEVICES] = {};                                                                 \
         if (lds > 64 * 1024) { const int rc_ = vcla_raise_dyn_lds((const void*)kern, lds, attr_set); if (rc_) return rc_; } \
         kern<<<grid, (NWM_) * 64, lds, s>>>(*a);                                                                     \
+        label = "attn_vit_kernel<" #NWM_ ">";                                                                        \
     }
+    const char* label = "";       // names the form (vcla_debug_last_launch)
     const int vit_form = vcla_knobs_get().attn_vit;   // 1 = register-staged form, 2 = direct-to-LDS pipelined form (257 tokens)
     const bool o16 = vcla_aligned(a->o, 16) && a->o_bs % 8 == 0 && a->o_hs % 8 == 0 && a->o_rs % 8 == 0;     // the DMA form stores O in 16-byte pieces
     if (a->Tq == 257 && vit_form != 1 && o16) {
@@ -1240,10 +1242,11 @@ int vcla_attention_vit(const vcla_attn_args* a, void* stream) {
         const int rc_ = vcla_raise_dyn_lds((const void*)kern, lds, attr_set);
         if (rc_) return rc_;
         kern<<<grid, 256, lds, s>>>(*a);
+        label = "attn_vit_dma_kernel";
     } else if (a->Tq == 257) VIT_GO(4)
     else VIT_GO(1)
 #undef VIT_GO
-    VCLA_CHECK_LAUNCH("attn_vit_kernel");
+    VCLA_CHECK_LAUNCH(label);
     return VCLA_OK;
 }
 
@@ -1276,6 +1279,7 @@ int vcla_attention_mfma(const vcla_attn_args* a, void* stream) {
     if (!a->causal && !a->key_mask && a->Tk > FA_KV && a->Tk % FA_KV >= 1 && a->Tk % FA_KV <= 4) kv -= a->Tk % FA_KV;
     const int ntiles = (kv + FA_KV - 1) / FA_KV;
     const int whole_env = vcla_knobs_get().attn_mfma_whole;   // A/B runs: 0 = always tile by tile
+    const char* label = "";       // names the instantiation (vcla_debug_last_launch)
 #define FA_GO(D_, NW_, MAXT_)                                                                                        \
     {                                                                                                                \
         auto kern = attn_mfma_kernel<D_, NW_, MAXT_>;                                                                \
@@ -1283,6 +1287,7 @@ int vcla_attention_mfma(const vcla_attn_args* a, void* stream) {
         static bool attr_set[VCLA_MAX_DEVICES] = {};                                                                 \
         if (lds > 64 * 1024) { const int rc_ = vcla_raise_dyn_lds((const void*)kern, lds, attr_set); if (rc_) return rc_; } \
         kern<<<grid, (NW_) * 64, lds, s>>>(*a);                                                                      \
+        label = "attn_mfma_kernel<" #D_ ", " #NW_ ", " #MAXT_ ">";                                                   \
     }
     if (a->D == 128) {
         // causal prefill: a 128-token prompt is 2 tiles = 64 KiB (two 4-wave workgroups per CU): 75.0 -> 54.6 us per layer at B = 64.
@@ -1298,6 +1303,6 @@ int vcla_attention_mfma(const vcla_attn_args* a, void* stream) {
         FA_GO(64, 4, 0)
     }
 #undef FA_GO
-    VCLA_CHECK_LAUNCH("attn_mfma_kernel");
+    VCLA_CHECK_LAUNCH(label);
     return VCLA_OK;
 }

@@ -266,10 +266,10 @@ static int launch_verify(const void* qkv, void* kc, void* vc, const float* cos_t
     const int S = verify_splits(ctx_max);
     attn_verify_kernel<T, D><<<dim3(H, S), NT, 0, s>>>((const T*)qkv, (T*)kc, (T*)vc, cos_tab, sin_tab, (T*)out, scratch, R, H, ctx_max, pos0,
                                                        pos_dev, key_mask, scale, out_frag);
-    VCLA_CHECK_LAUNCH("attn_verify_kernel");
+    VCLA_CHECK_LAUNCH(S > 1 ? "attn_verify_kernel<split>" : "attn_verify_kernel<S=1>");
     if (S > 1) {
         attn_verify_merge_kernel<T, D><<<H, NT, 0, s>>>(scratch, (T*)out, R, H, S, out_frag);
-        VCLA_CHECK_LAUNCH("attn_verify_merge_kernel");
+        VCLA_CHECK_LAUNCH("attn_verify_merge_kernel");      // (runs only behind attn_verify_kernel<split>)
     }
     return VCLA_OK;
 }

@@ -927,15 +927,17 @@ int vcla_engine_launch(const vcla_engine_args* a, hipStream_t s) {
     static bool attr_set[4][VCLA_MAX_DEVICES] = {};
     // the kernel with the split attention only for caches that can outgrow split_min (a captured step is replayed at every position up to ctx_max)
     const bool sk = a->split_min > 0 && a->ctx_max > a->split_min;
+    const char* label = "";       // names the instantiation (vcla_debug_last_launch)
 #define EG_GO(MASK_, SK_, I_)                                                                                                  \
     {                                                                                                                          \
         const int rc = vcla_raise_dyn_lds((const void*)decode_engine_kernel<MASK_, SK_>, EG_LDS_BYTES, attr_set[I_]);          \
         if (rc) return rc;                                                                                                     \
         decode_engine_kernel<MASK_, SK_><<<EG_NCU, 256, EG_LDS_BYTES, s>>>(*a);                                                \
+        label = "decode_engine_kernel<MASK=" #MASK_ ",SPLITK=" #SK_ ">";                                                       \
     }
     if (a->key_mask) { if (sk) EG_GO(true, true, 3) else EG_GO(true, false, 1) }
     else { if (sk) EG_GO(false, true, 2) else EG_GO(false, false, 0) }
 #undef EG_GO
-    VCLA_CHECK_LAUNCH("decode_engine_kernel");
+    VCLA_CHECK_LAUNCH(label);
     return VCLA_OK;
 }

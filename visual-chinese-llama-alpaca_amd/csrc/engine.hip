@@ -37,6 +37,7 @@ int vcla_fail(int code, const char* fmt, ...) {
 }
 extern "C" const char* vcla_last_error(void) { return g_err; }
 extern "C" int vcla_version(void) { return VCLA_ABI_VERSION; }
+extern "C" const char* vcla_debug_last_launch(void) { return vcla_last_launch; }
 
 extern "C" int vcla_device_check(void) {
     int dev = 0;

@@ -28,8 +28,13 @@ int vcla_fail(int code, const char* fmt, ...);
                              __FILE__, __LINE__);                                             \
     } while (0)
 
+// the label of the calling thread's most recent launch (vcla_debug_last_launch): a test can ask which instantiation its call
+// selected.  One host pointer store per launch; the labels are string literals.
+inline thread_local const char* vcla_last_launch = "";
+
 #define VCLA_CHECK_LAUNCH(name)                                                               \
     do {                                                                                      \
+        vcla_last_launch = (name);                                                            \
         hipError_t _e = hipGetLastError();                                                    \
         if (_e != hipSuccess)                                                                 \
             return vcla_fail(VCLA_ERR_HIP, "launch of %s failed: %s", name, hipGetErrorString(_e)); \

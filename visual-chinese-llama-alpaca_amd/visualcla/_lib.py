@@ -329,6 +329,7 @@ _vp, _i, _i64, _f, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
 SYMBOLS = {
     "vcla_version": (_i, []),
     "vcla_last_error": (C.c_char_p, []),
+    "vcla_debug_last_launch": (C.c_char_p, []),
     "vcla_device_check": (_i, []),
     "vcla_layernorm": (_i, [_vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _f, _i, _vp]),
     "vcla_rmsnorm": (_i, [_vp, _i64, _vp, _vp, _i64, _i, _i, _f, _i, _vp]),
@@ -424,6 +425,11 @@ def check(rc: int) -> None:
         if rc in (1, 2, 5):
             raise ValueError(f"visualcla_hip[{kind}]: {msg}")
         raise VclaError(f"visualcla_hip[{kind}]: {msg}")
+
+
+def last_launch() -> str:
+    """label of this thread's most recent kernel launch (vcla_debug_last_launch): which instantiation a dispatcher selected"""
+    return load().vcla_debug_last_launch().decode("ascii")
 
 
 def stream_ptr() -> int:
