@@ -791,6 +791,37 @@ int vcla_llama_decode_slots_constrained(vcla_ctx* ctx, const vcla_slot_args* slo
                                         const int32_t* eos_rows, const vcla_sample_row* rows, const vcla_logprob_args* logprobs,
                                         const vcla_constrain_args* constraints, void* stream);
 
+/* ---------------------------------------------------------------- stop sequences decided on the device (slots)
+   HF ends a request on a token sequence through a stopping criterion evaluated on the host after every step: StopStringCriteria /
+   a user StoppingCriteria over `input_ids` (hf:generation/stopping_criteria.py StoppingCriteriaList.__call__, reached from the
+   per-token loop of hf:generation/utils.py `unfinished_sequences & ~stopping_criteria(input_ids, scores)`,
+   models/visualcla/modeling_visualcla.py:382-391); the reference's front ends carry such stops (`custom_stopping_strings`).  Here a
+   request's stop sequences are a row of a table in DEVICE memory and the bookkeeping launch of the step decides them, so the captured
+   graph is kept and no step returns to the host.  Only GENERATED tokens are looked at, never the prompt (what such a criterion sees
+   behind input_ids[:, prompt_len:]).  Additive entries; the ABI version stays 5. */
+#define VCLA_SLOT_MAX_STOPS 4
+#define VCLA_SLOT_MAX_STOP_LEN 16
+typedef struct vcla_stop_args {
+    const int32_t* seqs;         /* [B][VCLA_SLOT_MAX_STOPS][VCLA_SLOT_MAX_STOP_LEN] device memory: token ids, every sequence left-aligned
+                                    and padded with -1; a row of -1 is no sequence                                                   */
+} vcla_stop_args;
+
+/* vcla_slot_step_rows plus stop sequences: stops NULL is that function (the same kernel instantiation, launch for launch).  Otherwise
+   an active slot b ALSO finishes when, with this step's id appended, the last len ids it generated (history[count[b] - len + 1 ..
+   count[b] - 1][b], then ids[b]) equal one of its sequences of length len >= 1; a sequence longer than what the slot generated so far
+   cannot match.  The stop ids are stored like any other id; eos, budget and everything else are unchanged.  One lane of the
+   workgroup's first wave per (sequence, offset): 4 x 16 = 64. */
+int vcla_slot_step_stops(const int64_t* ids, const vcla_slot_args* args, const int32_t* eos_rows, const vcla_stop_args* stops,
+                         const void* embed_table, void* x, int D, int V, int dtype, void* stream);
+
+/* vcla_llama_decode_slots_constrained whose bookkeeping launch is vcla_slot_step_stops: stops NULL is that function -- the same
+   launches and the same graph key.  Otherwise the table pointer is part of the graph key; the table lives in device memory and the
+   host rewrites the rows of the slots it fills between two calls, as it does eos_rows. */
+int vcla_llama_decode_slots_stops(vcla_ctx* ctx, const vcla_slot_args* slots, int n_steps, void* kv_cache, int ctx_max,
+                                  const int32_t* key_mask, void* ws, size_t ws_bytes, int use_graph, const vcla_sample_args* sampling,
+                                  const int32_t* eos_rows, const vcla_sample_row* rows, const vcla_logprob_args* logprobs,
+                                  const vcla_constrain_args* constraints, const vcla_stop_args* stops, void* stream);
+
 /* ---------------------------------------------------------------- debug */
 /* The label of the calling thread's most recent kernel launch through this library ("" before the first): a string literal that
    names the kernel and, for the attention dispatchers (vcla_attention, vcla_attn_decode_*, vcla_attn_verify, the persistent decode

@@ -1428,10 +1428,12 @@ extern "C" int vcla_llama_verify_loop(vcla_ctx* ctx, const vcla_lookup_args* arg
 // decoder's workspace.  Part of the graph key.
 // constraints (vcla_llama_decode_slots_constrained, csrc/constrain.hip): the mask on the row the selector reads -- the lm_head's logits, or
 // with logprobs the copy, which the stats pass then writes on the argmax path too -- and the transition on the ids taken.  Part of the graph key.
-extern "C" int vcla_llama_decode_slots_constrained(vcla_ctx* ctx, const vcla_slot_args* slots, int n_steps, void* kv_cache, int ctx_max,
-                                                   const int32_t* key_mask, void* ws, size_t ws_bytes, int use_graph, const vcla_sample_args* sampling,
-                                                   const int32_t* eos_rows, const vcla_sample_row* rows, const vcla_logprob_args* logprobs,
-                                                   const vcla_constrain_args* constraints, void* stream) {
+// stops (vcla_llama_decode_slots_stops, csrc/slots.hip): per-slot stop sequences in device memory, decided by the bookkeeping launch.  Null: the
+// launches and the graph key of the entry without them; otherwise the table pointer extends the key.
+extern "C" int vcla_llama_decode_slots_stops(vcla_ctx* ctx, const vcla_slot_args* slots, int n_steps, void* kv_cache, int ctx_max,
+                                             const int32_t* key_mask, void* ws, size_t ws_bytes, int use_graph, const vcla_sample_args* sampling,
+                                             const int32_t* eos_rows, const vcla_sample_row* rows, const vcla_logprob_args* logprobs,
+                                             const vcla_constrain_args* constraints, const vcla_stop_args* stops, void* stream) {
     VCLA_KNOBS_SCOPE();
     VCLA_REQUIRE(ctx && ctx->finalized && ctx->c.t_layers > 0, VCLA_ERR_BAD_ARG, "llama_decode_slots: context not finalized, or vision-only");
     RUN(slot_args_check(slots, "llama_decode_slots"));
@@ -1470,6 +1472,7 @@ extern "C" int vcla_llama_decode_slots_constrained(vcla_ctx* ctx, const vcla_slo
         VCLA_REQUIRE(c.t_vocab <= VCLA_CS_MAX_VOCAB, VCLA_ERR_BAD_SHAPE, "llama_decode_slots_constrained: vocab_size=%d (the bitmask of a row lives in LDS: max %d)",
                      c.t_vocab, VCLA_CS_MAX_VOCAB);
     }
+    VCLA_REQUIRE(!stops || stops->seqs, VCLA_ERR_BAD_ARG, "llama_decode_slots_stops: a null stop table");
     if (n_steps == 0) return VCLA_OK;
     hipStream_t s = (hipStream_t)stream;
     LlamaWs w;
@@ -1488,11 +1491,13 @@ extern "C" int vcla_llama_decode_slots_constrained(vcla_ctx* ctx, const vcla_slo
         else RUN(vcla_argmax(sel, c.t_vocab, w.ids, B, c.t_vocab, st));
         if (logprobs) RUN(vcla_logprob_pick(w.logits, c.t_vocab, B, c.t_vocab, slots->hist_len, slots->hist_cap, logprobs, lp_lse, w.ids, st));
         if (constraints) RUN(vcla_constrain_advance(w.ids, B, slots->hist_len, constraints, st));
-        return vcla_slot_step_rows(w.ids, slots, eos_rows, ctx->embed, w.x, c.t_hidden, c.t_vocab, c.act_dtype, st);
+        return vcla_slot_step_stops(w.ids, slots, eos_rows, stops, ctx->embed, w.x, c.t_hidden, c.t_vocab, c.act_dtype, st);
     };
-    struct { const void *kv_cache, *key_mask, *ws, *eos_rows, *rows; int ctx_max, has_samp; vcla_slot_args slots; vcla_sample_args samp;
-             int has_lp; vcla_logprob_args lp; int has_cs; vcla_constrain_args cs; } key;
-    memset(&key, 0, sizeof key);
+    struct Key { const void *kv_cache, *key_mask, *ws, *eos_rows, *rows; int ctx_max, has_samp; vcla_slot_args slots; vcla_sample_args samp;
+                 int has_lp; vcla_logprob_args lp; int has_cs; vcla_constrain_args cs; };
+    struct { Key k; const void* stop_seqs; } key_stops;   // with a stop table: the key without one, then the table pointer
+    memset(&key_stops, 0, sizeof key_stops);
+    Key& key = key_stops.k;
     key.kv_cache = kv_cache; key.key_mask = key_mask; key.ws = ws; key.ctx_max = ctx_max; key.has_samp = sampling != nullptr;
     key.eos_rows = eos_rows; key.rows = rows;
     memcpy(&key.slots, slots, sizeof(*slots));
@@ -1501,7 +1506,17 @@ extern "C" int vcla_llama_decode_slots_constrained(vcla_ctx* ctx, const vcla_slo
     if (logprobs) memcpy(&key.lp, logprobs, sizeof(*logprobs));
     key.has_cs = constraints != nullptr;
     if (constraints) memcpy(&key.cs, constraints, sizeof(*constraints));
-    return run_steps(ctx->slots_graph, "slots", key, use_graph, n_steps, s, one_step);
+    if (!stops) return run_steps(ctx->slots_graph, "slots", key, use_graph, n_steps, s, one_step);
+    key_stops.stop_seqs = stops->seqs;
+    return run_steps(ctx->slots_graph, "slots", key_stops, use_graph, n_steps, s, one_step);
+}
+
+extern "C" int vcla_llama_decode_slots_constrained(vcla_ctx* ctx, const vcla_slot_args* slots, int n_steps, void* kv_cache, int ctx_max,
+                                                   const int32_t* key_mask, void* ws, size_t ws_bytes, int use_graph, const vcla_sample_args* sampling,
+                                                   const int32_t* eos_rows, const vcla_sample_row* rows, const vcla_logprob_args* logprobs,
+                                                   const vcla_constrain_args* constraints, void* stream) {
+    return vcla_llama_decode_slots_stops(ctx, slots, n_steps, kv_cache, ctx_max, key_mask, ws, ws_bytes, use_graph, sampling, eos_rows, rows, logprobs,
+                                         constraints, nullptr, stream);
 }
 
 extern "C" int vcla_llama_decode_slots_logprobs(vcla_ctx* ctx, const vcla_slot_args* slots, int n_steps, void* kv_cache, int ctx_max,

@@ -266,6 +266,39 @@ def slot_args(eos_ids, row_pos, count, budget, hist_len, history, cur, summary):
     return a
 
 
+SLOT_MAX_STOPS = 4          # VCLA_SLOT_MAX_STOPS: stop sequences of one request
+SLOT_MAX_STOP_LEN = 16      # VCLA_SLOT_MAX_STOP_LEN: ids of one stop sequence
+
+
+class StopArgs(C.Structure):
+    _fields_ = [("seqs", C.c_void_p)]
+
+
+def slot_stop_rows(stop_rows) -> torch.Tensor:
+    """per-slot lists of stop sequences -> int32 host tensor [B, SLOT_MAX_STOPS, SLOT_MAX_STOP_LEN], every sequence left-aligned and -1
+    padded (the table of vcla_slot_step_stops).  The launcher cannot check a table in device memory: counts, lengths and ids >= 0 are
+    checked HERE, before the upload"""
+    out = torch.full((len(stop_rows), SLOT_MAX_STOPS, SLOT_MAX_STOP_LEN), -1, dtype=torch.int32)
+    for b, seqs in enumerate(stop_rows):
+        seqs = [[int(x) for x in q] for q in (seqs or [])]
+        if len(seqs) > SLOT_MAX_STOPS:
+            raise ValueError(f"slot {b}: at most {SLOT_MAX_STOPS} stop sequences (got {len(seqs)})")
+        for k, q in enumerate(seqs):
+            if not 1 <= len(q) <= SLOT_MAX_STOP_LEN or min(q) < 0:
+                raise ValueError(f"slot {b}: stop sequence {k} must hold 1..{SLOT_MAX_STOP_LEN} non-negative ids (got {q})")
+            out[b, k, :len(q)] = torch.tensor(q, dtype=torch.int32)
+    return out
+
+
+def stop_args(seqs) -> StopArgs:
+    """vcla_stop_args over the device table int32 [B, SLOT_MAX_STOPS, SLOT_MAX_STOP_LEN]; the struct holds a bare pointer: the tensor must stay alive"""
+    if seqs.dtype != torch.int32 or seqs.dim() != 3 or tuple(seqs.shape[1:]) != (SLOT_MAX_STOPS, SLOT_MAX_STOP_LEN) or not seqs.is_contiguous():
+        raise ValueError(f"stop_args: the table must be a contiguous int32 [B, {SLOT_MAX_STOPS}, {SLOT_MAX_STOP_LEN}] tensor")
+    a = StopArgs()
+    a.seqs = seqs.data_ptr()
+    return a
+
+
 LOGPROB_MAX_K = 20          # VCLA_LOGPROB_MAX_K
 
 
@@ -395,6 +428,9 @@ SYMBOLS = {
     "vcla_constrain_advance": (_i, [_vp, _i, _vp, C.POINTER(ConstrainArgs), _vp]),
     "vcla_llama_decode_slots_constrained": (_i, [_vp, C.POINTER(SlotArgs), _i, _vp, _i, _vp, _vp, _sz, _i, C.POINTER(SampleArgs), _vp, _vp,
                                                  C.POINTER(LogprobArgs), C.POINTER(ConstrainArgs), _vp]),
+    "vcla_slot_step_stops": (_i, [_vp, C.POINTER(SlotArgs), _vp, C.POINTER(StopArgs), _vp, _vp, _i, _i, _i, _vp]),
+    "vcla_llama_decode_slots_stops": (_i, [_vp, C.POINTER(SlotArgs), _i, _vp, _i, _vp, _vp, _sz, _i, C.POINTER(SampleArgs), _vp, _vp,
+                                           C.POINTER(LogprobArgs), C.POINTER(ConstrainArgs), C.POINTER(StopArgs), _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -20,6 +20,8 @@ from typing import Callable, Dict, List, Optional, Sequence
 RequestOutput = namedtuple("RequestOutput", ["tokens", "logprobs", "top_ids", "top_logprobs"])
 
 LOGPROB_MAX_K = 20          # VCLA_LOGPROB_MAX_K
+SLOT_MAX_STOPS = 4          # VCLA_SLOT_MAX_STOPS
+SLOT_MAX_STOP_LEN = 16      # VCLA_SLOT_MAX_STOP_LEN
 
 
 def check_logprobs(logprobs) -> Optional[int]:
@@ -31,17 +33,67 @@ def check_logprobs(logprobs) -> Optional[int]:
     return int(logprobs)
 
 
+def check_stop_sequences(requests_stops: Sequence, vocab_size: int, forced: Optional[Sequence[bool]] = None) -> List[Optional[List[List[int]]]]:
+    """the `stop_sequences` key of every request (None: the request has none) -> host lists of ints.  At most SLOT_MAX_STOPS sequences of 1 to
+    SLOT_MAX_STOP_LEN ids from the vocabulary, never beside target_ids (forced[i]); every refusal names its request, all in ONE message"""
+    bad, out = [], []
+    for i, seqs in enumerate(requests_stops):
+        if seqs is None:
+            out.append(None)
+            continue
+        why = []
+        if forced is not None and forced[i]:
+            why.append("stop_sequences beside target_ids (a forced request ends with its targets)")
+        if isinstance(seqs, (str, bytes)) or not hasattr(seqs, "__len__") or any(isinstance(q, (str, bytes)) or not hasattr(q, "__len__") for q in seqs):
+            why.append("stop_sequences must be a list of lists of token ids")
+            seqs = []
+        seqs = [q.tolist() if hasattr(q, "tolist") else list(q) for q in seqs]
+        if len(seqs) > SLOT_MAX_STOPS:
+            why.append(f"{len(seqs)} stop sequences (at most {SLOT_MAX_STOPS})")
+        for k, q in enumerate(seqs):
+            if not len(q):
+                why.append(f"stop sequence {k} is empty")
+            elif len(q) > SLOT_MAX_STOP_LEN:
+                why.append(f"stop sequence {k} holds {len(q)} ids (at most {SLOT_MAX_STOP_LEN})")
+            if any(isinstance(x, bool) or not isinstance(x, int) for x in q):
+                why.append(f"stop sequence {k} holds non-integers")
+            elif not all(0 <= x < vocab_size for x in q):
+                why.append(f"stop sequence {k} holds ids outside the vocabulary 0..{vocab_size - 1}")
+        if why:
+            bad.append(f"request {i}: " + ", ".join(why))
+        out.append([[int(x) for x in q] for q in seqs] if not why else None)
+    if bad:
+        raise ValueError("generate_many: " + "; ".join(bad))
+    return out
+
+
+def stop_hit(tokens: Sequence[int], seqs) -> bool:
+    """does the tail of `tokens` equal one of `seqs`?  (the brute-force statement of the stopping criterion)"""
+    return any(len(q) <= len(tokens) and list(tokens[len(tokens) - len(q):]) == list(q) for q in (seqs or []) if len(q))
+
+
+def cut_at_stop(tokens: Sequence[int], seqs) -> List[int]:
+    """`tokens` cut behind the first position where one of `seqs` ends"""
+    tokens = list(tokens)
+    for n in range(1, len(tokens) + 1):
+        if stop_hit(tokens[:n], seqs):
+            return tokens[:n]
+    return tokens
+
+
 def round_up(x: int, m: int) -> int:
     return (int(x) + m - 1) // m * m
 
 
 def slot_step_model(ids: Sequence[int], row_pos: List[int], count: List[int], budget: Sequence[int], history: List[List[int]],
                     cur: List[int], eos_ids: Sequence[int], hist_len: Optional[List[int]] = None,
-                    eos_rows: Optional[Sequence[Sequence[int]]] = None) -> int:
+                    eos_rows: Optional[Sequence[Sequence[int]]] = None, stops: Optional[Sequence[Sequence[Sequence[int]]]] = None) -> int:
     """One step of the slot bookkeeping (csrc/slots.hip), in place: `ids[b]` is the id selected for slot b this step.  An active slot
     (row_pos[b] >= 0) stores it at history[count[b]][b], advances count and position, and finishes (row_pos[b] = -1) on an eos id or
     when count[b] reaches budget[b]; inactive slots are left alone.  eos_rows (vcla_slot_step_rows): one eos list per slot, used instead
-    of `eos_ids`.  Returns the number of slots still active."""
+    of `eos_ids`.  stops (vcla_slot_step_stops): the stop sequences of every slot; an active slot also finishes when the ids it generated, this step's
+    included, end in one of them (lane j of the kernel: token count - j against entry len - 1 - j; earlier tokens come from the history).
+    Returns the number of slots still active."""
     n_active = 0
     for b in range(len(row_pos)):
         if row_pos[b] < 0:
@@ -51,6 +103,9 @@ def slot_step_model(ids: Sequence[int], row_pos: List[int], count: List[int], bu
         if c < len(history):
             history[c][b] = t
         fin = c + 1 >= budget[b] or t in (eos_ids if eos_rows is None else eos_rows[b])
+        for q in (stops[b] if stops is not None else ()):
+            n = len(q)
+            fin = fin or (n >= 1 and all((t if j == 0 else history[c - j][b] if 0 <= c - j < len(history) else None) == q[n - 1 - j] for j in range(n)))
         count[b] = c + 1
         row_pos[b] = -1 if fin else row_pos[b] + 1
         if hist_len is not None:
@@ -84,11 +139,16 @@ class InflightScheduler:
     logprobs (k or None): with a value every finished request also carries its per-token arrays (`extra` of started / `extras_of` of
     after_chunk: (logprobs [n], top_ids [n][k], top_logprobs [n][k])), and ordered_results() returns RequestOutput tuples.  targets[i]
     (a list of ids, or None): request i is teacher-forced -- its budget is len(targets[i]), whatever budgets[i] says, and a target that
-    does not fit under max_position_embeddings raises instead of being clipped."""
+    does not fit under max_position_embeddings raises instead of being clipped.
+
+    stops[i] (lists of ids, or None): request i's stop sequences (checked by check_stop_sequences); the stepper decides them, the scheduler
+    counts them.  Streaming: deliver() hands the tokens every running request produced since its last call to a callback, in ascending
+    request order, and returns the slots whose callback asked to cancel; cancel() finishes such a request with what was delivered."""
 
     def __init__(self, prompt_lens: Sequence[int], budgets: Sequence[int], has_image: Sequence[bool], max_batch: int,
                  max_position_embeddings: int, image_at_head: bool = False, steps_per_sync: int = 8, share_prefix: bool = False,
-                 logprobs: Optional[int] = None, targets: Optional[Sequence[Optional[Sequence[int]]]] = None):
+                 logprobs: Optional[int] = None, targets: Optional[Sequence[Optional[Sequence[int]]]] = None,
+                 stops: Optional[Sequence[Optional[Sequence[Sequence[int]]]]] = None):
         if max_batch < 1:
             raise ValueError(f"max_batch must be at least 1 (got {max_batch})")
         if steps_per_sync < 1:
@@ -104,6 +164,9 @@ class InflightScheduler:
             raise ValueError(f"targets has {len(self.targets)} entries for {len(prompt_lens)} requests")
         if self.logprobs is None and any(x is not None for x in self.targets):
             raise ValueError("targets need logprobs")
+        self.stops: List[Optional[List[List[int]]]] = [None if x is None or not len(x) else [list(q) for q in x] for x in (stops or [None] * len(prompt_lens))]
+        if len(self.stops) != len(prompt_lens):
+            raise ValueError(f"stops has {len(self.stops)} entries for {len(prompt_lens)} requests")
         budgets = [b if x is None else len(x) for b, x in zip(budgets, self.targets)]
         for i, (t, b) in enumerate(zip(self.T, budgets)):
             if self.max_pos - t <= 0:
@@ -125,8 +188,10 @@ class InflightScheduler:
         self.results: Dict[int, List[int]] = {}
         self.extras: Dict[int, tuple] = {}                       # logprobs: request -> (logprobs, top_ids, top_logprobs)
         self.decode_from: Dict[int, int] = {}                    # request -> T of its admission group = the position its slot decoded from
+        self.sent: Dict[int, List[int]] = {}                     # streaming: request -> the tokens delivered to the callback so far
+        self.first_ended: List[tuple] = []                       # streaming: (request, its only token) of requests their first token ended, not yet delivered
         self.stats = {"requests": self.n, "slots": self.slots, "steps": 0, "tokens": 0, "admission_groups": 0, "slot_steps_active": 0,
-                      "slot_steps_total": 0}
+                      "slot_steps_total": 0, "stop_requests": sum(x is not None for x in self.stops), "stop_hits": 0, "cancelled": 0, "stream_calls": 0}
 
     # ------------------------------------------------------------------ admission
     def free_slots(self) -> List[int]:
@@ -177,19 +242,58 @@ class InflightScheduler:
             self.extras[i] = tuple(list(x) for x in extra)
         self.results[i] = [int(t) for t in tokens]
         self.stats["tokens"] += len(tokens)
+        self.stats["stop_hits"] += stop_hit(self.results[i], self.stops[i])
         self.slot_req[b] = None
 
+    def cancel(self, b: int, tokens: Sequence[int], extra=None) -> None:
+        """The callback cancelled slot b's request at this boundary: it is complete with the tokens delivered so far (extra: their
+        arrays) and the slot is free for the next admission.  The stepper switches the slot off (row_pos = hist_len = -1)."""
+        self._finish(b, tokens, extra)
+        self.stats["cancelled"] += 1
+
+    def first_stop(self, i: int, first_token: int) -> bool:
+        """does request i's first token alone complete one of its stop sequences?"""
+        return stop_hit([int(first_token)], self.stops[i])
+
     def started(self, b: int, first_token: int, ended: bool, extra=None) -> None:
-        """The first token of slot b's request came out of its prefill.  ended (an eos, or a budget of 1): the request is complete and
-        never occupies the slot past this boundary.  extra (logprobs): the arrays of that one token."""
+        """The first token of slot b's request came out of its prefill.  ended (an eos, a budget of 1, a one-token stop sequence): the
+        request is complete and never occupies the slot past this boundary.  extra (logprobs): the arrays of that one token."""
         if ended:
+            self.first_ended.append((self.slot_req[b], int(first_token)))
             self._finish(b, [first_token], extra)
+
+    # ------------------------------------------------------------------ streaming
+    def deliver_first(self, on_tokens: Optional[Callable]) -> None:
+        """the one call (finished=True) of every request its first token ended since the last call, in ascending request order"""
+        ended, self.first_ended = sorted(self.first_ended), []
+        for i, tok in ended if on_tokens is not None else ():
+            self.stats["stream_calls"] += 1
+            on_tokens(i, [tok], True)
+
+    def deliver(self, on_tokens: Callable, row_pos: Sequence[int], count: Sequence[int], new_tokens: Callable[[int, int, int], Sequence[int]]) -> List[int]:
+        """After a chunk, before after_chunk: on_tokens(request, tokens, finished) for every running request, in ascending request order,
+        with the tokens [n0, n1) it produced since its last call -- new_tokens(slot, n0, n1).  Returns the slots whose callback returned
+        a true value while the request was still running: the caller cancels them.  `sent` keeps what was delivered."""
+        cancelled = []
+        for i, b in sorted((i, b) for b, i in enumerate(self.slot_req) if i is not None):
+            got = self.sent.setdefault(i, [])
+            n0, n1 = len(got), int(count[b])
+            if n1 <= n0:
+                continue
+            toks = [int(t) for t in new_tokens(b, n0, n1)]
+            got.extend(toks)
+            self.stats["stream_calls"] += 1
+            if on_tokens(i, toks, row_pos[b] < 0) and row_pos[b] >= 0:
+                cancelled.append(b)
+        return cancelled
 
     # ------------------------------------------------------------------ after a chunk of steps
     def after_chunk(self, n_steps: int, row_pos: Sequence[int], count: Sequence[int], tokens_of: Callable[[int, int], Sequence[int]],
-                    count_before: Optional[Sequence[int]] = None, extras_of: Optional[Callable[[int, int], tuple]] = None) -> List[int]:
+                    count_before: Optional[Sequence[int]] = None, extras_of: Optional[Callable[[int, int], tuple]] = None,
+                    cancelled: Sequence[int] = ()) -> List[int]:
         """n_steps steps ran.  Slots whose request finished (row_pos < 0) are harvested -- tokens_of(slot, n) returns the slot's n tokens,
-        extras_of(slot, n) (logprobs) its per-token arrays -- and freed.  Returns them."""
+        extras_of(slot, n) (logprobs) its per-token arrays -- and freed; so are the `cancelled` ones (deliver's), with the count[b] tokens
+        they were delivered.  Returns them."""
         self.stats["steps"] += n_steps
         self.stats["slot_steps_total"] += n_steps * self.slots
         done = []
@@ -198,8 +302,8 @@ class InflightScheduler:
                 continue
             if count_before is not None:
                 self.stats["slot_steps_active"] += int(count[b]) - int(count_before[b])
-            if row_pos[b] < 0:
-                self._finish(b, tokens_of(b, int(count[b])), extras_of(b, int(count[b])) if extras_of is not None else None)
+            if row_pos[b] < 0 or b in cancelled:
+                (self.cancel if b in cancelled else self._finish)(b, tokens_of(b, int(count[b])), extras_of(b, int(count[b])) if extras_of is not None else None)
                 done.append(b)
         return done
 
@@ -236,16 +340,21 @@ def static_batch_steps(budgets: Sequence[int], slots: int) -> int:
 
 def simulate(budgets: Sequence[int], slots: int, steps_per_sync: int, eos_at: Optional[Dict[int, int]] = None, prompt_lens=None, has_image=None,
              max_position_embeddings: int = 1 << 20, image_at_head: bool = False, share_prefix: bool = False, logprobs: Optional[int] = None,
-             targets=None):
+             targets=None, stops=None, on_tokens: Optional[Callable] = None, token_of: Optional[Callable[[int, int], int]] = None):
     """Drives a scheduler with the host model of the slot step and a stepper that emits token (request, k) = 1000 * request + k, or the
     eos id 0 as request i's eos_at[i]-th token.  Returns (scheduler, log of (boundary, slot, request) admissions).
     logprobs / targets: the scheduler's; a forced request emits its targets instead, and token t of request i scores
-    -(i + t / 1000) with top ids [t * 10 + r] and top logprobs [-(i + r)] (a stand-in for the device buffers)."""
+    -(i + t / 1000) with top ids [t * 10 + r] and top logprobs [-(i + r)] (a stand-in for the device buffers).
+    stops: the scheduler's (per request); the slot table carries them as the device table does.  on_tokens: the streaming callback of
+    generate_many, called as the slots loop calls it; a true return value cancels.  token_of(i, k): request i's k-th token (1-based)
+    instead of 1000 * (i + 1) + k."""
     n = len(budgets)
     eos_at = eos_at or {}
     sch = InflightScheduler(prompt_lens or [4] * n, budgets, has_image or [False] * n, slots, max_position_embeddings, image_at_head, steps_per_sync,
-                            share_prefix, logprobs, targets)
+                            share_prefix, logprobs, targets, stops)
     B = sch.slots
+    use_stops = any(x is not None for x in sch.stops)
+    slot_stops: List[List[List[int]]] = [[] for _ in range(B)]
     row_pos, count, bud, cur = [-1] * B, [0] * B, [0] * B, [0] * B
     history = [[0] * B for _ in range(sch.cap)]
     log = []
@@ -254,6 +363,8 @@ def simulate(budgets: Sequence[int], slots: int, steps_per_sync: int, eos_at: Op
     def tok(i, k):
         if sch.targets[i] is not None:
             return sch.targets[i][k - 1]
+        if token_of is not None:
+            return int(token_of(i, k))
         return 0 if eos_at.get(i) == k else 1000 * (i + 1) + k
 
     def extra(i, m):                                             # what the device buffers of request i hold for its first m tokens
@@ -271,18 +382,23 @@ def simulate(budgets: Sequence[int], slots: int, steps_per_sync: int, eos_at: Op
                 for i, b in zip(g.requests, g.slots):
                     log.append((boundary, b, i))
                     first = tok(i, 1)
-                    ended = first == 0 or sch.budget[i] == 1
+                    ended = first == 0 or sch.budget[i] == 1 or sch.first_stop(i, first)
                     sch.started(b, first, ended, extra(i, 1))
                     if not ended:
                         row_pos[b], count[b], bud[b], cur[b] = sch.decode_from[i], 1, sch.budget[i], first
                         history[0][b] = first
+                        slot_stops[b] = sch.stops[i] or []
+            sch.deliver_first(on_tokens)
         if sch.finished:
             break
         before = list(count)
         for _ in range(steps_per_sync):
             ids = [tok(sch.slot_req[b], count[b] + 1) if sch.slot_req[b] is not None and row_pos[b] >= 0 else -7 for b in range(B)]
-            slot_step_model(ids, row_pos, count, bud, history, cur, [0])
+            slot_step_model(ids, row_pos, count, bud, history, cur, [0], stops=slot_stops if use_stops else None)
+        cancelled = sch.deliver(on_tokens, row_pos, count, lambda b, n0, n1: [history[k][b] for k in range(n0, n1)]) if on_tokens is not None else []
+        for b in cancelled:
+            row_pos[b] = -1
         sch.after_chunk(steps_per_sync, row_pos, count, lambda b, m: [history[k][b] for k in range(m)], before,
-                        (lambda b, m: extra(sch.slot_req[b], m)) if sch.logprobs is not None else None)
+                        (lambda b, m: extra(sch.slot_req[b], m)) if sch.logprobs is not None else None, cancelled)
         boundary += 1
     return sch, log

@@ -166,9 +166,48 @@ def chat(model, image: Union[str, "Image.Image", torch.Tensor], text: str, histo
     return response, history
 
 
+class TextStops:
+    """The string side of chat_many(stop=..., stops=..., on_text=...), as generate_many's `on_tokens` callback: item i's tokens so far are
+    decoded (skip_special_tokens=True) at every boundary; the earliest occurrence of any of its strings cancels the item, and cut() is the
+    text before it.  strings_of[i]: item i's stop strings (the queue's `stop` followed by its own entry of `stops`)."""
+
+    def __init__(self, tokenizer, n_items: int, stop=None, stops=None, on_text=None):
+        if stops is not None and len(stops) != n_items:
+            raise ValueError(f"chat_many: stops has {len(stops)} entries for {n_items} items")
+        if on_text is not None and not callable(on_text):
+            raise ValueError("chat_many: on_text must be a callable fn(i, text_so_far, finished) or None")
+        if isinstance(stop, str):
+            stop = [stop]
+        self.strings_of = [list(stop or []) + list((stops[i] if stops is not None else None) or []) for i in range(n_items)]
+        for i, strings in enumerate(self.strings_of):
+            if any(not isinstance(x, str) or not x for x in strings):
+                raise ValueError(f"chat_many: item {i}: stop strings must be non-empty str (got {strings!r})")
+        self.tokenizer, self.on_text, self.tokens = tokenizer, on_text, [[] for _ in range(n_items)]
+
+    @property
+    def active(self) -> bool:
+        return self.on_text is not None or any(self.strings_of)
+
+    def cut(self, i: int, text: str) -> str:
+        """`text` before the earliest occurrence of any of item i's strings"""
+        at = [p for p in (text.find(x) for x in self.strings_of[i]) if p >= 0]
+        return text[:min(at)] if at else text
+
+    def on_tokens(self, i: int, new, finished: bool) -> bool:
+        self.tokens[i].extend(new)
+        if self.on_text is None and not self.strings_of[i]:
+            return False
+        text = self.tokenizer.decode(self.tokens[i], skip_special_tokens=True)
+        kept = self.cut(i, text)
+        hit = len(kept) < len(text)
+        if self.on_text is not None:
+            self.on_text(i, kept, bool(finished or hit))
+        return hit
+
+
 @torch.inference_mode()
 def chat_many(model, items, generation_config=None, max_batch=64, share_prefix=False, generation_configs=None, seeds=None, prefix_cache=None,
-              logprobs=None, constraints=None):
+              logprobs=None, constraints=None, stop=None, stops=None, on_text=None):
     """The bulk form of chat(): items = [(image, text) or (image, text, history), ...] -> [(response, history), ...].  Every prompt is built as
     chat() builds it, the queue is answered by model.generate_many (in-flight batching over max_batch slots) and every response is appended
     to its item's history exactly as chat() appends it.  share_prefix: generate_many's switch -- the system prompt every item begins with and the
@@ -180,7 +219,15 @@ def chat_many(model, items, generation_config=None, max_batch=64, share_prefix=F
     RequestOutput(tokens, logprobs, top_ids, top_logprobs) -- the log-probabilities of the RAW distribution, before any processor or
     warper of the config, one row per generated token.  `target_ids` is not offered here.
     constraints: an optional list with one entry per item, None or a dict with exactly one of generate_many's request keys
-    `allowed_token_ids`, `banned_token_ids`, `choices` (token ids; string-level choices are not offered), forwarded as that key."""
+    `allowed_token_ids`, `banned_token_ids`, `choices` (token ids; string-level choices are not offered), forwarded as that key.
+    stop=[str, ...] (every item) / stops=[per item: None or [str, ...]] (the item's own, behind the queue's): stop STRINGS, built on
+    generate_many's `on_tokens`.  At every boundary of the slots loop an item with strings decodes all its tokens so far
+    (skip_special_tokens=True); the earliest occurrence of any of its strings cancels the item, and its response and history entry are
+    the text BEFORE that occurrence (the final chunk is checked too).  Token-level output (RequestOutput.tokens with logprobs) holds what
+    was delivered: it can run up to generate_many's steps_per_sync tokens past the string.  Strings are NOT converted into generate_many's
+    `stop_sequences`: a sentencepiece tokenisation depends on context, so no token sequence stands for a string.
+    on_text=fn: the streamed form, fn(i, text_so_far, finished) once per boundary for every item that produced tokens, text_so_far
+    already cut at a stop string; exactly one call per item has finished=True and it is the last."""
     from . import constraints as _constraints
     from .inflight import check_logprobs
     logprobs = check_logprobs(logprobs)
@@ -199,6 +246,7 @@ def chat_many(model, items, generation_config=None, max_batch=64, share_prefix=F
         histories.append(history)
     if not encs:
         return []
+    text_stops = TextStops(model.tokenizer, len(items), stop, stops, on_text)
     requests = [dict(input_ids=e.input_ids[0], attention_mask=e.attention_mask[0], pixel_values=e.pixel_values) for e in encs]
     for i, r in enumerate(requests):
         if generation_configs is not None and generation_configs[i] is not None:
@@ -211,10 +259,11 @@ def chat_many(model, items, generation_config=None, max_batch=64, share_prefix=F
             r.update(constraints[i])
     outs = model.generate_many(requests, max_batch=max_batch, generation_config=gc, share_prefix=share_prefix,
                                **({} if prefix_cache is None else dict(prefix_cache=prefix_cache)),
-                               **({} if logprobs is None else dict(logprobs=logprobs)))
+                               **({} if logprobs is None else dict(logprobs=logprobs)),
+                               **(dict(on_tokens=text_stops.on_tokens) if text_stops.active else {}))
     results = []
-    for out, history in zip(outs, histories):
-        response = model.tokenizer.decode(out if logprobs is None else out.tokens, skip_special_tokens=True)
+    for i, (out, history) in enumerate(zip(outs, histories)):
+        response = text_stops.cut(i, model.tokenizer.decode(out if logprobs is None else out.tokens, skip_special_tokens=True))
         history.append({"type": "response", "value": response})
         results.append((response, history) if logprobs is None else (response, history, out))
     return results

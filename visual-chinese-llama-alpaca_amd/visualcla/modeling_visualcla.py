@@ -1225,11 +1225,12 @@ class VisualCLAModel:
     def _inflight_request(self, i: int, r, logprobs: Optional[int] = None) -> dict:
         """one entry of generate_many's `requests` -> ids [T] int64, pixel_values [C, H, W] or None, attention_mask [T] or None (on the device);
         `target` (a host list of ids, or None): the request's target_ids -- only with `logprobs`, never beside max_new_tokens;
-        `constraint`: the spec of its allowed_token_ids / banned_token_ids / choices key (visualcla/constraints.py), or None"""
+        `constraint`: the spec of its allowed_token_ids / banned_token_ids / choices key (visualcla/constraints.py), or None;
+        `stops`: its stop_sequences key as given (inflight.check_stop_sequences checks the whole queue's, in one message), or None"""
         from . import constraints
         if not isinstance(r, dict) or r.get("input_ids") is None:
             raise ValueError(f"request {i}: a dict with `input_ids` is required")
-        unknown = set(r) - {"input_ids", "pixel_values", "attention_mask", "max_new_tokens", "generation_config", "seed", "target_ids", *constraints.KEYS}
+        unknown = set(r) - {"input_ids", "pixel_values", "attention_mask", "max_new_tokens", "generation_config", "seed", "target_ids", "stop_sequences", *constraints.KEYS}
         if unknown:
             raise ValueError(f"request {i}: unknown keys {sorted(unknown)}")
         constraint = constraints.parse(i, r)                      # host lists: checked before anything moves to the device
@@ -1267,7 +1268,7 @@ class VisualCLAModel:
                 raise ValueError(f"request {i}: target_ids must be a 1-D sequence of at least one integer id (got shape {tuple(tg.shape)}, {tg.dtype})")
             target = [int(x) for x in tg.tolist()]
         return dict(ids=ids, px=row(r.get("pixel_values"), 3, "pixel_values"), am=am, max_new_tokens=mnt, generation_config=rc, seed=seed,
-                    target=target, constraint=constraint)
+                    target=target, constraint=constraint, stops=r.get("stop_sequences"))
 
     def _request_configs(self, gc, reqs):
         """the resolved generation config of every request -> (configs, class of every request, one config per class).  A request without
@@ -1363,7 +1364,7 @@ class VisualCLAModel:
     @torch.no_grad()
     def generate_many(self, requests, max_batch: int = 64, generation_config=None, steps_per_sync: int = 8, use_graph: Optional[bool] = None,
                       share_prefix: bool = False, prefix_pool_tokens: Optional[int] = None, prefix_cache=None, logprobs: Optional[int] = None,
-                      **kwargs):
+                      on_tokens=None, **kwargs):
         """In-flight batching over a queue: -> List[LongTensor [n_i]] in request order, the NEW tokens of every request, its eos included
         and nothing behind it.  requests: dicts with `input_ids` ([T] or [1, T]), optional `pixel_values`, `attention_mask`, `max_new_tokens`
         (default: the config's budget by generate()'s rules for that prompt), `generation_config`, `seed`.
@@ -1419,10 +1420,28 @@ class VisualCLAModel:
         memory; the captured step masks the row the selector reads and moves every slot's state, without returning to the host.
         `logprobs` stay RAW: they do not see the constraint.  Not beside `target_ids`; `choices` needs an eos_token_id and excludes
         no_repeat_ngram_size and a min-token floor.  A queue of one constrained request (or max_batch=1) takes the slots route at one
-        slot.  last_inflight_stats gains `constrained_requests`, `automaton_nodes`, `automaton_edges`."""
-        from .inflight import InflightScheduler, RequestOutput, check_logprobs
+        slot.  last_inflight_stats gains `constrained_requests`, `automaton_nodes`, `automaton_edges`.
+
+        Stop sequences (csrc/slots.hip): the request key `stop_sequences=[[ids...], ...]`, host lists of at most 4
+        sequences of 1 to 16 token ids.  The request ends at the first step after which the tail of its GENERATED tokens (never the
+        prompt) equals one of them; the stop tokens are returned and nothing comes behind them, as with an eos.  min_new_tokens does
+        not delay a stop, a budget that ends inside a sequence is no match, and whichever of eos, stop and budget comes first ends
+        the request.  result[i] is generate() of request i alone under a stopping criterion "the generated tail equals one of these
+        sequences" = the result of the same call without the key, cut behind the first position where a sequence ends.  The captured
+        step decides it per slot from a table in device memory.  Not beside `target_ids`.
+
+        on_tokens=fn: streaming.  fn(i, tokens: List[int], finished: bool) is called once per boundary (every `steps_per_sync` steps)
+        for every request that produced tokens since its last call, in ascending request index within a boundary; the chunks of
+        request i concatenate to result[i] (its `.tokens` with logprobs), exactly one call per request has finished=True and it is
+        the last, a chunk holds at most steps_per_sync + 1 tokens.  A call that returns a true value CANCELS its request at this
+        boundary: the request is complete with the tokens delivered so far (with logprobs, their arrays) and its slot is refilled
+        at once.  An exception raised by fn propagates.  With `stop_sequences` or `on_tokens` a queue of one request (or max_batch=1)
+        takes the slots route at one slot.  last_inflight_stats holds `stop_requests`, `stop_hits`, `cancelled`, `stream_calls`."""
+        from .inflight import InflightScheduler, RequestOutput, check_logprobs, check_stop_sequences
         from .prefix_cache import PrefixCache
         logprobs = check_logprobs(logprobs)                       # before anything else: the argument by name
+        if on_tokens is not None and not callable(on_tokens):
+            raise ValueError(f"generate_many: on_tokens must be a callable fn(i, tokens, finished) or None (got {type(on_tokens).__name__})")
         if prefix_cache is not None:
             if not share_prefix:
                 raise ValueError("generate_many: prefix_cache needs share_prefix=True (only the ragged admission of share_prefix places a request "
@@ -1437,6 +1456,7 @@ class VisualCLAModel:
         for i, tg in enumerate(targets):
             if tg is not None and not all(0 <= x < t["vocab_size"] for x in tg):
                 raise ValueError(f"request {i}: target_ids outside the vocabulary 0..{t['vocab_size'] - 1}")
+        stops = check_stop_sequences([r["stops"] for r in reqs], t["vocab_size"], [tg is not None for tg in targets])
         if logprobs and t["vocab_size"] > _lib.SAMPLE_MAX_VOCAB:
             raise ValueError(f"generate_many: logprobs={logprobs} with vocab_size={t['vocab_size']} (the top-k pass holds a row of at most "
                              f"{_lib.SAMPLE_MAX_VOCAB} logits in registers; logprobs=0 has no such limit)")
@@ -1471,13 +1491,15 @@ class VisualCLAModel:
             extra_stats.update(ctable.stats())
         # raises for a prompt that leaves no room, by index, before any kernel runs
         sched = InflightScheduler(lens, budgets, [r["px"] is not None for r in reqs], max_batch, t["max_position_embeddings"], self.image_at_head,
-                                  steps_per_sync, share_prefix=bool(share_prefix), logprobs=logprobs, targets=targets)
+                                  steps_per_sync, share_prefix=bool(share_prefix), logprobs=logprobs, targets=targets, stops=stops)
+        slots_only = prefix_cache is not None or logprobs is not None or ctable is not None or on_tokens is not None or any(x is not None for x in sched.stops)
         if use_graph is None:
             use_graph = os.environ.get("VCLA_DECODE_GRAPH", "1") != "0"
-        if sched.slots == 1 and ((prefix_cache is None and logprobs is None and ctable is None) or not reqs):
+        if sched.slots == 1 and (not slots_only or not reqs):
             # max_batch = 1 or a single request: generate() per request (the persistent B = 1 step is the fast path there).  With a prefix
             # cache such a queue stays on the slots route, at one slot: generate() has no place for cached rows; with logprobs too: the
-            # persistent B = 1 step folds its greedy tail and produces no logits; with a constrained request for the same reason
+            # persistent B = 1 step folds its greedy tail and produces no logits; with a constrained request for the same reason; with stop
+            # sequences or a token callback because only the slots loop decides the one and has the boundaries of the other
             out = []
             for i, r in enumerate(reqs):
                 self._request_seed = seeds[i]                     # the private hook _draw_uniforms reads: no public argument of generate()
@@ -1513,7 +1535,7 @@ class VisualCLAModel:
             side.wait_stream(cur_stream)
         with torch.cuda.device(self._device), torch.cuda.stream(side if side is not None else cur_stream):
             try:
-                out = slots_run.SlotsRun(self, class_gcs[0], reqs, sched, bool(use_graph), plan, gcs if len(class_gcs) > 1 else None, seeds, pstate, logprobs, ctable).run()
+                out = slots_run.SlotsRun(self, class_gcs[0], reqs, sched, bool(use_graph), plan, gcs if len(class_gcs) > 1 else None, seeds, pstate, logprobs, ctable, on_tokens).run()
             except BaseException:
                 if pstate is not None:                            # the index may name blocks whose copies were never enqueued
                     prefix_cache.end()

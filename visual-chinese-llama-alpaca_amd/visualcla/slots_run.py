@@ -1,5 +1,5 @@
 """The slots loop of VisualCLAModel.generate_many (DESIGN.md sections 7c-7h): one SlotsRun per call holds the buffers, the scheduler and
-what the features switched on add -- PerRequest (per-slot eos lists and sampler records, 7f), Logprobs (7h), Constraints (7i), PrefixShare (7e, 7g); None
+what the features switched on add -- PerRequest (per-slot eos lists and sampler records, 7f), Logprobs (7h), Constraints (7i), Stops (7j), PrefixShare (7e, 7g); None
 where the feature is off -- and admits, steps and harvests until the queue is empty.  The model (`self.m`) keeps its kernels' wrappers."""
 from __future__ import annotations
 
@@ -39,6 +39,15 @@ class Constraints:
 
     def __init__(self, table, nodes: torch.Tensor, edges: torch.Tensor, state: torch.Tensor):
         self.table, self.nodes, self.edges, self.state, self.args = table, nodes, edges, state, _lib.constrain_args(nodes, edges, state)
+
+
+class Stops:
+    """a queue with stop sequences: the per-slot table int32 [B, SLOT_MAX_STOPS, SLOT_MAX_STOP_LEN] (-1: no entry; every slot starts without
+    sequences) and the step's vcla_stop_args over it"""
+    __slots__ = ("table", "args")
+
+    def __init__(self, table: torch.Tensor):
+        self.table, self.args = table, _lib.stop_args(table)
 
 
 class PrefixShare:
@@ -139,10 +148,14 @@ class SlotsRun:
     """gcs None: one config `gc` for the whole queue.  Else gcs[i] is request i's config, there are at least two distinct ones, and the
     step reads per-slot tables (_per_request_tables).  pstate: the call's state of a prefix cache (PrefixCache.begin), or None.
     logprobs (k or None): the step also runs the stats pass and the pick (csrc/logprobs.hip); sched.targets[i] forces request i.
-    constraints (a constraints.Table or None): the step also runs the mask and the transition (csrc/constrain.hip)."""
+    constraints (a constraints.Table or None): the step also runs the mask and the transition (csrc/constrain.hip).
+    sched.stops[i]: request i's stop sequences -- with any, the bookkeeping launch of the step decides them from a per-slot table.
+    on_tokens (a callable or None): every boundary hands each running request's new tokens to it; a true return value cancels the request."""
+    stops = on_tokens = None    # (the defaults of a run assembled by hand, as the host tests do)
 
-    def __init__(self, model, gc, reqs, sched, use_graph, plan=None, gcs=None, seeds=None, pstate=None, logprobs=None, constraints=None):
+    def __init__(self, model, gc, reqs, sched, use_graph, plan=None, gcs=None, seeds=None, pstate=None, logprobs=None, constraints=None, on_tokens=None):
         self.m, self.reqs, self.sched, self.use_graph, self.dev = model, reqs, sched, use_graph, model._device
+        self.on_tokens = on_tokens
         self.lib = lib = _lib.load()
         t, B, ctx_max, cap, W = model.config.text_config, sched.slots, sched.ctx_max, sched.cap, _lib.SLOT_SUMMARY_WORDS
         self.seeds = seeds if seeds is not None else [None] * sched.n
@@ -182,6 +195,9 @@ class SlotsRun:
         self.cons = None
         if constraints is not None:                             # the table is uploaded once; every slot starts unconstrained
             self.cons = Constraints(constraints, *constraints.tensors(self.dev), model._typed_buf("if_cs_state", (B,), torch.int32).fill_(-1))
+        self.stops = None
+        if any(x is not None for x in sched.stops):
+            self.stops = Stops(model._typed_buf("if_stops", (B, _lib.SLOT_MAX_STOPS, _lib.SLOT_MAX_STOP_LEN), torch.int32).fill_(-1))
         self.slot_args = _lib.slot_args(eos, row_pos, count, budget, hist_len, hist, cur, summary)
         self.samp = _lib.sample_args(uniforms=uni, history=hist, **samp_kw) if samp_kw is not None else None
         self.count_h, self.share = [0] * B, None
@@ -201,10 +217,13 @@ class SlotsRun:
                     self.fill_forced(groups)
                 if self.cons is not None:
                     self.fill_state(groups)
+                if self.stops is not None:
+                    self.fill_stops(groups)
                 for g in groups:
                     if self.per is not None:
                         self.fill_rows(g.requests, g.slots)
                     (self.admit_ragged if g.ragged else self.admit_padded)(g)
+                sched.deliver_first(self.on_tokens)             # the requests their first token ended: their one call
             t1 = time.perf_counter()
             t_adm += t1 - t0
             if sched.finished:
@@ -242,6 +261,11 @@ class SlotsRun:
         """the automaton state of every slot that is filled: the request's root node, -1 = unconstrained (first_token then moves it)"""
         pairs = [(b, self.cons.table.roots[i]) for g in groups for i, b in zip(g.requests, g.slots)]
         self.cons.state[torch.tensor([b for b, _ in pairs], device=self.dev)] = torch.tensor([r for _, r in pairs], dtype=torch.int32, device=self.dev)
+
+    def fill_stops(self, groups) -> None:
+        """the stop sequences of every slot that is filled (a row of -1: none), rewritten between two chunks of steps as fill_rows does"""
+        pairs = [(b, self.sched.stops[i]) for g in groups for i, b in zip(g.requests, g.slots)]
+        self.stops.table[torch.tensor([b for b, _ in pairs], device=self.dev)] = _lib.slot_stop_rows([q for _, q in pairs]).to(self.dev)
 
     def fill_rows(self, requests, slots) -> None:
         """admission: the table rows of the slots it fills, rewritten between two chunks of steps"""
@@ -305,11 +329,11 @@ class SlotsRun:
         return first
 
     def start_slots(self, requests, slots, first_tokens, row_pos_of) -> None:
-        """the tail of an admission: first_tokens[j] came out of the prefill of requests[j] in slots[j].  A request it ends (an eos, a budget of 1) never
+        """the tail of an admission: first_tokens[j] came out of the prefill of requests[j] in slots[j].  A request it ends (an eos, a budget of 1, a one-token stop sequence) never
         occupies the slot; the others get their slot state.  row_pos_of: where the slots decode from -- one int (a left-padded group) or a table by request"""
         sched, st, B, live = self.sched, self.st, self.sched.slots, []
         for i, b, tok in zip(requests, slots, first_tokens):
-            ended = tok in (self.eos if self.per is None else self.per.eos_of[i]) or sched.budget[i] == 1
+            ended = tok in (self.eos if self.per is None else self.per.eos_of[i]) or sched.budget[i] == 1 or (self.stops is not None and sched.first_stop(i, tok))
             sched.started(b, tok, ended, self.lp.first.pop(i) if self.lp is not None else None)
             if not ended:
                 live.append((i, b, tok))
@@ -426,21 +450,38 @@ class SlotsRun:
         self.start_slots(g.requests, g.slots, [first_of[i] for i in g.requests], plan.T)      # every slot decodes from its own T
 
     def decode_chunk(self, n: int) -> None:
-        """n steps of every live slot, one call; the per-slot tables, the logprob block and the constraints are null where the feature is off"""
+        """n steps of every live slot, one call; the per-slot tables, the logprob block, the constraints and the stop table are null where the feature is off"""
         per, ws = self.per, self.ws
-        _lib.check(self.lib.vcla_llama_decode_slots_constrained(
+        _lib.check(self.lib.vcla_llama_decode_slots_stops(
             self.m._ctx, C.byref(self.slot_args), n, self.kv.data_ptr(), self.sched.ctx_max, self.km.data_ptr(), ws.data_ptr(), ws.numel(),
             int(self.use_graph), C.byref(self.samp) if self.samp is not None else None, per.eos_dev.data_ptr() if per is not None else None,
             _lib.ptr(per.rows_dev) if per is not None else None, C.byref(self.lp.args) if self.lp is not None else None,
-            C.byref(self.cons.args) if self.cons is not None else None, _lib.stream_ptr()))
+            C.byref(self.cons.args) if self.cons is not None else None, C.byref(self.stops.args) if self.stops is not None else None,
+            _lib.stream_ptr()))
 
     def harvest(self, host) -> None:
-        """`host`: the slot table after a chunk.  The finished slots' columns of the history and of the logprob buffers go to the scheduler"""
+        """`host`: the slot table after a chunk.  The finished slots' columns of the history and of the logprob buffers go to the scheduler.
+        on_tokens: first the history rows touched since the last boundary come to the host in ONE copy (instead of the finished slots' columns: the
+        scheduler keeps what it delivered), every running request's new tokens go to the callback, and the slots it cancels are switched off on the
+        device before the next chunk and harvested with the finished ones"""
         sched, lp, B = self.sched, self.lp, self.sched.slots
         pos_h, cnt_h = host[:B], host[B:2 * B]
-        done = [b for b in range(B) if sched.slot_req[b] is not None and pos_h[b] < 0]
+        cancelled, streaming = [], self.on_tokens is not None
+        live = [b for b in range(B) if sched.slot_req[b] is not None]
+        if streaming and live:
+            lo, hi = min(len(sched.sent.get(sched.slot_req[b], ())) for b in live), max(cnt_h[b] for b in live)
+            rows = self.hist[lo:hi].tolist()
+            cancelled = sched.deliver(self.on_tokens, pos_h, cnt_h, lambda b, n0, n1: [rows[k - lo][b] for k in range(n0, n1)])
+            if cancelled:
+                ci = torch.tensor(cancelled, device=self.dev)
+                self.st[ci] = -1                                # row_pos
+                self.st[2 * B + ci] = -1                        # hist_len
+        done = [b for b in live if pos_h[b] < 0 or b in cancelled]
         di = torch.tensor(done, device=self.dev) if done else None
-        cols = dict(zip(done, self.hist[:, di].t().tolist())) if done else {}
+        if streaming:
+            cols = {b: sched.sent[sched.slot_req[b]] for b in done}
+        else:
+            cols = dict(zip(done, self.hist[:, di].t().tolist())) if done else {}
         extras_of = None
         if lp is not None:
             lcols = dict(zip(done, lp.lp[:, di].t().tolist())) if done else {}
@@ -449,5 +490,5 @@ class SlotsRun:
 
             def extras_of(b, m):
                 return lcols[b][:m], (icols[b][:m] if icols is not None else [[]] * m), (tcols[b][:m] if tcols is not None else [[]] * m)
-        sched.after_chunk(sched.steps_per_sync, pos_h, cnt_h, lambda b, m: cols[b][:m], self.count_h, extras_of)
+        sched.after_chunk(sched.steps_per_sync, pos_h, cnt_h, lambda b, m: cols[b][:m], self.count_h, extras_of, cancelled)
         self.count_h = cnt_h
