@@ -822,6 +822,42 @@ int vcla_llama_decode_slots_stops(vcla_ctx* ctx, const vcla_slot_args* slots, in
                                   const int32_t* eos_rows, const vcla_sample_row* rows, const vcla_logprob_args* logprobs,
                                   const vcla_constrain_args* constraints, const vcla_stop_args* stops, void* stream);
 
+/* ---------------------------------------------------------------- a paged K/V cache for the slots (block tables)
+   HF's cache is one tensor per layer, [B, H, T, d], grown for the whole batch (hf:cache_utils.py DynamicCache.update, reached from
+   LlamaAttention.forward hf:llama/modeling_llama.py:217-281): every row pays for the longest.  Here the slots may share ONE POOL of
+   blocks of VCLA_KV_BLOCK_ROWS rows, [L][2][H][n_blocks * 16][d] -- the slots layout with a single sequence of n_blocks * 16 rows, so a
+   (layer, K or V, head) slab stays one buffer -- and a table in DEVICE memory says where each slot's rows live: logical key j of slot b
+   is physical row table[b * ld + (j >> 4)] * 16 + (j & 15) of the head's slab.  Sizes and bounds (the inactive test, the score buffer,
+   key_mask_ld) follow the LOGICAL cap ctx_cap; only addresses follow the pool.  The host owns the table: it validates every row before
+   the upload (entries in range, no block owned twice, enough blocks for the rows the slot will write).  The kernels never form an
+   address from an entry outside [0, n_blocks): such a key counts as masked and an append through it is skipped.
+   Additive entries; the ABI version stays 5. */
+typedef struct vcla_kv_pages {
+    const int32_t* table;        /* [B][ld] device memory: pool block of logical block (row / 16) of every slot, -1 = none            */
+    int ld;                      /* words per table row, ld * 16 >= ctx_cap                                                          */
+    int n_blocks;                /* blocks in the pool                                                                                */
+} vcla_kv_pages;
+
+/* Bytes of a pool of n_blocks blocks for this context's decoder (bf16 / fp32 rows; 0 on a bad argument). */
+size_t vcla_kv_pool_bytes(const vcla_ctx* ctx, int n_blocks);
+
+/* vcla_attn_decode_rows over the pool: k_pool / v_pool are [H][n_blocks * 16][d], row_pos[b] outside [0, ctx_cap) is an inactive
+   sequence, key_mask rows are over LOGICAL positions (key_mask_ld >= ctx_cap).  Same lane-to-key assignment, batch order and arithmetic
+   as vcla_attn_decode_rows: output and appended row equal that entry on a contiguous cache holding the same rows, bit for bit.  fp32 /
+   bf16, head dim 64 / 128, no VCLA_KV_FP8; a head's slab stays below 4 GiB (16 M rows at d = 128 in bf16). */
+int vcla_attn_decode_paged(const void* qkv, void* k_pool, void* v_pool, const float* cos_tab, const float* sin_tab, void* out, int B, int H,
+                           int d, int ctx_cap, const int32_t* row_pos, const vcla_kv_pages* pages, const int32_t* key_mask, int64_t key_mask_ld,
+                           float scale, int dtype, int out_frag, void* stream);
+
+/* vcla_llama_decode_slots_stops over the pool: pages NULL is that function -- the same launches and the same graph key.  Otherwise
+   kv_cache is the pool, ctx_max the logical cap of a slot, the attention launch of every layer is vcla_attn_decode_paged and the struct
+   extends the graph key; the table POINTER is stable for a call and the host rewrites the rows of the slots it fills between two calls,
+   so a captured step replays unchanged. */
+int vcla_llama_decode_slots_paged(vcla_ctx* ctx, const vcla_slot_args* slots, int n_steps, void* kv_cache, int ctx_max,
+                                  const int32_t* key_mask, void* ws, size_t ws_bytes, int use_graph, const vcla_sample_args* sampling,
+                                  const int32_t* eos_rows, const vcla_sample_row* rows, const vcla_logprob_args* logprobs,
+                                  const vcla_constrain_args* constraints, const vcla_stop_args* stops, const vcla_kv_pages* pages, void* stream);
+
 /* ---------------------------------------------------------------- debug */
 /* The label of the calling thread's most recent kernel launch through this library ("" before the first): a string literal that
    names the kernel and, for the attention dispatchers (vcla_attention, vcla_attn_decode_*, vcla_attn_verify, the persistent decode

@@ -9,6 +9,11 @@
 // ROWS (vcla_attn_decode_rows, in-flight batching): one position PER SEQUENCE instead -- `pos_dev` is then the vector row_pos[B] and
 // workgroup (h, b) works at row_pos[b]; a sequence whose position is outside [0, ctx_max) is inactive: nothing is appended, its output
 // row is zero.  Same code otherwise: row b equals, bit for bit, the uniform form at pos = row_pos[b].
+// PAGED (vcla_attn_decode_paged, always with ROWS): the cache is a pool [H][n_blocks * 16][d] per layer and K / V, and logical key j of
+// sequence b lives at physical row table[b * ld + (j >> 4)] * 16 + (j & 15) of the head's slab; `ctx_max` is then the LOGICAL cap (inactive
+// test, score buffer, key mask), only addresses take the pool.  A table entry outside [0, n_blocks) is never turned into an address: the
+// key counts as masked, the append is skipped.  Same lane-to-key assignment, batch order and arithmetic: bit for bit the ROWS form on a
+// contiguous cache that holds the same rows.
 #include "vcla_common.h"
 #include <stdlib.h>
 
@@ -48,6 +53,16 @@ template <> __device__ __forceinline__ void load8<bf16_t>(const bf16_t* p, float
 
 // 8 consecutive elements of a cache row, still in the storage dtype: lets the V rows be FETCHED before the softmax (the loads
 // do not depend on the scores) and converted afterwards
+// the block table of a paged launch (vcla_kv_pages, by value)
+struct KvPages { const int32_t* table; int ld; int n_blocks; };
+// The table is never written by a kernel that reads it: the constant address space says so, and a load at a wave-uniform index is then a
+// scalar load (through the generic pointer the loads inside the flash kernel's loop stay vector loads the wave must wait for in order)
+typedef const __attribute__((address_space(4))) int32_t* kv_table_p;
+// physical row of logical key j through one table word, or -1 for a word outside [0, n_blocks)
+__device__ __forceinline__ int paged_row(int word, int j, int n_blocks) {
+    return (unsigned)word < (unsigned)n_blocks ? word * VCLA_KV_BLOCK_ROWS + (j & (VCLA_KV_BLOCK_ROWS - 1)) : -1;
+}
+
 template <typename T> struct Raw8;
 template <> struct Raw8<float> {
     float4 a, b;
@@ -69,12 +84,13 @@ template <> struct Raw8<bf16_t> {
 // NW = waves per workgroup.  4 everywhere except the batch form at short contexts (NW = 2, see launch_decode): the batch launch
 // is bounded by the dependent chain of a workgroup times the number of ROUNDS of workgroups, not by bandwidth; 2-wave
 // workgroups fit 8 per CU, i.e. B * H = 2048 (b, h) pairs in ONE round instead of two.
-template <typename T, int D, bool COOP, int NW = 4, bool ROWS = false>
+template <typename T, int D, bool COOP, int NW = 4, bool ROWS = false, bool PAGED = false>
 __global__ __launch_bounds__(NW * 64) void attn_decode_kernel(const T* __restrict__ qkv, T* __restrict__ kc, T* __restrict__ vc,
                                                           const float* __restrict__ cos_tab, const float* __restrict__ sin_tab,
                                                           T* __restrict__ out, int H, int ctx_max, int pos0,
                                                           const int32_t* __restrict__ pos_dev, const int32_t* __restrict__ key_mask,
-                                                          int64_t key_mask_ld, float scale, int sc_cap, int out_frag_mt) {
+                                                          int64_t key_mask_ld, float scale, int sc_cap, int out_frag_mt, KvPages pg = KvPages{}) {
+    static_assert(!PAGED || ROWS, "the paged form is a per-row form");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* qs = smem;              // [D]   roped query
     float* knew = smem + D;        // [D]   roped new key
@@ -82,6 +98,7 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kernel(const T* __restric
     float* red = smem + 3 * D;     // [2 * NW]
     float* part = smem + 3 * D + 2 * NW;  // [NW][D] partial outputs
     float* sc = part + NW * D;     // [sc_cap] scores / probabilities
+    int* tb = reinterpret_cast<int*>(sc + sc_cap);   // PAGED: [ceil((pos + 1) / 16)] first physical row of each block of the sequence, -1 = none
     constexpr int NT = NW * 64;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int h = blockIdx.x, b = blockIdx.y;
@@ -104,8 +121,20 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kernel(const T* __restric
         }
     }
     const T* row = qkv + (int64_t)b * 3 * HD;
-    T* kbase = kc + ((int64_t)b * H + h) * ctx_max * D;
-    T* vbase = vc + ((int64_t)b * H + h) * ctx_max * D;
+    T* kbase = kc + (PAGED ? (int64_t)h * pg.n_blocks * VCLA_KV_BLOCK_ROWS : ((int64_t)b * H + h) * ctx_max) * D;
+    T* vbase = vc + (PAGED ? (int64_t)h * pg.n_blocks * VCLA_KV_BLOCK_ROWS : ((int64_t)b * H + h) * ctx_max) * D;
+    // row of the cache that takes the new key / value: `pos`, or its place in the pool (< 0: no valid block, the append is skipped)
+    int arow = pos;
+    if constexpr (PAGED) {
+        const int32_t* trow = pg.table + (int64_t)b * pg.ld;
+        arow = paged_row(trow[pos >> 4], pos, pg.n_blocks);
+        for (int i = tid; i <= (pos >> 4); i += NT) tb[i] = paged_row(trow[i], 0, pg.n_blocks);   // read behind the barrier below
+    }
+    // physical row of cached key j (PAGED: through the LDS copy of the table row; < 0 = the key has no block and counts as masked)
+    auto prow_of = [&](int j) -> int {
+        if constexpr (PAGED) { const int r0 = tb[j >> 4]; return r0 < 0 ? -1 : r0 + (j & (VCLA_KV_BLOCK_ROWS - 1)); }
+        else return j;
+    };
 
     // ---- RoPE on q and k_new (rotate-half form), stage q/k/v in LDS, append k/v to the cache
     if (tid < HALF) {
@@ -116,20 +145,22 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kernel(const T* __restric
         const float k0 = Act<T>::ld(row + HD + h * D + tid), k1 = Act<T>::ld(row + HD + h * D + tid + HALF);
         const float r0 = Act<T>::rnd(k0 * c - k1 * s), r1 = Act<T>::rnd(k1 * c + k0 * s);
         knew[tid] = r0; knew[tid + HALF] = r1;
-        Act<T>::st(kbase + (int64_t)pos * D + tid, r0);
-        Act<T>::st(kbase + (int64_t)pos * D + tid + HALF, r1);
+        if (!PAGED || arow >= 0) {
+            Act<T>::st(kbase + (int64_t)arow * D + tid, r0);
+            Act<T>::st(kbase + (int64_t)arow * D + tid + HALF, r1);
+        }
     } else if (NT >= 128 + D) {
         if (tid >= 128 && tid < 128 + D) {
             const int i = tid - 128;
             const float v = Act<T>::ld(row + 2 * HD + h * D + i);
             vnew[i] = v;
-            Act<T>::st(vbase + (int64_t)pos * D + i, v);
+            if (!PAGED || arow >= 0) Act<T>::st(vbase + (int64_t)arow * D + i, v);
         }
     } else {
         for (int i = tid - HALF; i < D; i += NT - HALF) {   // fewer threads than values: the threads past the RoPE lanes share them
             const float v = Act<T>::ld(row + 2 * HD + h * D + i);
             vnew[i] = v;
-            Act<T>::st(vbase + (int64_t)pos * D + i, v);
+            if (!PAGED || arow >= 0) Act<T>::st(vbase + (int64_t)arow * D + i, v);
         }
     }
     __syncthreads();
@@ -143,7 +174,8 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kernel(const T* __restric
 #pragma unroll
     for (int u = 0; u < UV; ++u) {
         const int j = vsub + u * KPB;
-        if (j < pos) vpre[u].load(vbase + (int64_t)j * D + vc_ * 8);   // predicated: no traffic for slots past the context
+        const int r = j < pos ? prow_of(j) : -1;
+        if (r >= 0) vpre[u].load(vbase + (int64_t)r * D + vc_ * 8);   // predicated: no traffic for slots past the context
         else vpre[u].zero();
     }
 
@@ -154,8 +186,9 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kernel(const T* __restric
     if constexpr (!COOP) {
         for (int j = tid; j < Tk; j += NT) {
             float sv;
-            if (km && km[j] == 0) sv = -INFINITY;
-            else if (j < pos) sv = scale * RowDot<T, D>::dot(qs, kbase + (int64_t)j * D);
+            const int r = j < pos ? prow_of(j) : 0;
+            if ((km && km[j] == 0) || (PAGED && r < 0)) sv = -INFINITY;
+            else if (j < pos) sv = scale * RowDot<T, D>::dot(qs, kbase + (int64_t)r * D);
             else {
                 float acc = 0.f;
 #pragma unroll 8
@@ -173,10 +206,13 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kernel(const T* __restric
         for (int e = 0; e < 8; ++e) qr[e] = qs[kc_ * 8 + e];
         for (int j0 = ksub; j0 < pos; j0 += KPB * UK) {
             Raw8<T> kr[UK];
+            bool kok[UK];
 #pragma unroll
             for (int u = 0; u < UK; ++u) {
                 const int j = j0 + u * KPB;
-                if (j < pos) kr[u].load(kbase + (int64_t)j * D + kc_ * 8);
+                const int r = j < pos ? prow_of(j) : -1;
+                kok[u] = r >= 0;
+                if (r >= 0) kr[u].load(kbase + (int64_t)r * D + kc_ * 8);
                 else kr[u].zero();
             }
 #pragma unroll
@@ -190,7 +226,7 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kernel(const T* __restric
                 for (int off = 1; off < LPK; off <<= 1) acc += __shfl_xor(acc, off, 64);
                 const int j = j0 + u * KPB;
                 if (kc_ == 0 && j < pos) {
-                    const float sv = (km && km[j] == 0) ? -INFINITY : scale * acc;
+                    const float sv = ((km && km[j] == 0) || (PAGED && !kok[u])) ? -INFINITY : scale * acc;
                     sc[j] = sv;
                     mx = fmaxf(mx, sv);
                 }
@@ -253,7 +289,8 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kernel(const T* __restric
             const int j = j0 + u * KPB;
             const bool ok = j < pos;
             pj[u] = ok ? sc[j] : 0.f;
-            if (ok) vr[u].load(vbase + (int64_t)j * D + vc_ * 8);
+            const int r = ok ? prow_of(j) : -1;
+            if (r >= 0) vr[u].load(vbase + (int64_t)r * D + vc_ * 8);
             else vr[u].zero();
         }
 #pragma unroll
@@ -382,12 +419,14 @@ __device__ __forceinline__ float fp8_round(float x) {
 // that read q / k / v sum the slices, apply what the GEMM epilogue would have (the deferred-RMSNorm rstd of the row from its 16 partial
 // sums of squares, the fp8 weight scale of the column) and round to bf16: the values the reduce launch would have stored.
 struct QkvParts { int64_t slice; const float* ssq; const float* w_scale; float inv_hidden, eps; };
-template <int D, int NW, bool MASK, bool KV8 = false, bool QP = false, bool ROWS = false>
+template <int D, int NW, bool MASK, bool KV8 = false, bool QP = false, bool ROWS = false, bool PAGED = false>
 __global__ __launch_bounds__(NW * 64, NW == 2 ? 4 : 2) void attn_decode_flash_kernel(const void* __restrict__ qkv_, void* __restrict__ kc_, void* __restrict__ vc_,
                                                                 const float* __restrict__ cos_tab, const float* __restrict__ sin_tab,
                                                                 bf16_t* __restrict__ out, int H, int ctx_max, int pos0,
                                                                 const int32_t* __restrict__ pos_dev, const int32_t* __restrict__ key_mask,
-                                                                int64_t key_mask_ld, float scale, int out_frag_mt, QkvParts qp = QkvParts{}) {
+                                                                int64_t key_mask_ld, float scale, int out_frag_mt, QkvParts qp = QkvParts{},
+                                                                KvPages pg = KvPages{}) {
+    static_assert(!PAGED || (ROWS && !KV8 && !QP), "the paged form is the per-row form over bf16 rows");
     // U keys per lane group and batch.  The 2-wave form (batch decode: thousands of workgroups, 4 waves per SIMD) keeps 2 x 4 rows of K
     // and V per lane in flight; the 4-wave form (a few dozen latency-bound workgroups: B = 1) 2 x 8 -- with D = 128 its 16 groups
     // then have the first 256 keys of the context requested before the RoPE phase ends
@@ -421,8 +460,14 @@ __global__ __launch_bounds__(NW * 64, NW == 2 ? 4 : 2) void attn_decode_flash_ke
     }
     const bf16_t* row = (const bf16_t*)qkv_ + (int64_t)b * 3 * HD;
     const float* prow = (const float*)qkv_ + (int64_t)b * 3 * HD;      // QP: slice 0 of this sequence's row
-    unsigned char* kbase = (unsigned char*)kc_ + ((int64_t)b * H + h) * ctx_max * D * ESZ;
-    unsigned char* vbase = (unsigned char*)vc_ + ((int64_t)b * H + h) * ctx_max * D * ESZ;
+    // PAGED: the slab of head h in the pool (one sequence of n_blocks * 16 rows); `ctx_max` stays the logical cap
+    const int slab_rows = PAGED ? pg.n_blocks * VCLA_KV_BLOCK_ROWS : ctx_max;
+    unsigned char* kbase = (unsigned char*)kc_ + (PAGED ? (int64_t)h : (int64_t)b * H + h) * slab_rows * D * ESZ;
+    unsigned char* vbase = (unsigned char*)vc_ + (PAGED ? (int64_t)h : (int64_t)b * H + h) * slab_rows * D * ESZ;
+    const kv_table_p trow = PAGED ? (kv_table_p)(uintptr_t)(pg.table + (int64_t)b * pg.ld) : nullptr;      // this sequence's row of the block table
+    // row of the cache that takes the new key / value: `pos`, or its place in the pool (< 0: no valid block, the append is skipped)
+    int arow = pos;
+    if constexpr (PAGED) arow = paged_row(trow[pos >> 4], pos, pg.n_blocks);
     const int32_t* km = key_mask ? key_mask + b * key_mask_ld : nullptr;
     const int c = lane % LPK, grp = wave * KPW + lane / LPK;   // chunk of the row, lane group within the workgroup
 
@@ -453,27 +498,56 @@ __global__ __launch_bounds__(NW * 64, NW == 2 ? 4 : 2) void attn_decode_flash_ke
     }
     u32x4_t kA[U], vA[U], kB[U], vB[U];
     int mA[U], mB[U];
+    // PAGED: the table words of the batch that the NEXT load of the ring slot takes, fetched a ring turn ahead.  They are wave-uniform
+    // (a wave's KPW <= 16 lane groups sit inside one 16-row block per u, see FD_TABLE), so they are scalar loads into SGPRs: no
+    // VGPR is spent on them
+    [[maybe_unused]] int tA[U], tB[U];
+    [[maybe_unused]] int okA = 0, okB = 0;     // PAGED: bit u = word u of the loaded batch names a block of the pool (wave-uniform too)
+    [[maybe_unused]] const int wave_g0 = __builtin_amdgcn_readfirstlane(wave) * KPW;    // first lane group of this wave
     const int last = pos > 0 ? pos - 1 : 0;
     // rows past the context are clamped to the last cached row (a line the group reads anyway) and masked at use: the loads
     // are unconditional, so the loop carries no branch around a load and the compiler emits counted waits
     // buffer loads (uniform descriptor per (b, h) slab + one 32-bit offset per row, non-temporal): no 64-bit address arithmetic in
     // the loop, and the policy bit survives (the plain nontemporal load builtin lost it once fences were nearby)
-    const __amdgpu_buffer_rsrc_t rK = __builtin_amdgcn_make_buffer_rsrc(kbase, 0, ctx_max * D * ESZ, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rV = __builtin_amdgcn_make_buffer_rsrc(vbase, 0, ctx_max * D * ESZ, 0x00020000);
-#define FD_LOAD(KB_, VB_, MB_, t_)                                                                                   \
+    const __amdgpu_buffer_rsrc_t rK = __builtin_amdgcn_make_buffer_rsrc(kbase, 0, slab_rows * D * ESZ, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rV = __builtin_amdgcn_make_buffer_rsrc(vbase, 0, slab_rows * D * ESZ, 0x00020000);
+    // PAGED: the table word of the keys of batch t_, one per u and wave.  The wave's keys of one u are j = j0 + x, x < KPW, with j0 a
+    // multiple of KPW and KPW dividing 16: they share block j0 >> 4.  Keys past the context are clamped to `last` (> j0 - KPW), whose
+    // block is the smaller of the two -- so min() is the block of EVERY lane's (clamped) key, and it stays inside the blocks the
+    // sequence owns.
+    static_assert(!PAGED || (KPW <= VCLA_KV_BLOCK_ROWS && VCLA_KV_BLOCK_ROWS % KPW == 0), "a wave's keys of one load sit in one block");
+#define FD_TABLE(TB_, t_)                                                                                            \
+    if constexpr (PAGED) {                                                                                           \
+        _Pragma("unroll") for (int u = 0; u < U; ++u) {                                                              \
+            const int j0_ = wave_g0 + ((t_) * U + u) * KPB;                                                          \
+            TB_[u] = trow[min(j0_ >> 4, last >> 4)];                                                                 \
+        }                                                                                                            \
+    }
+    // PAGED: the row comes through the table word fetched a ring turn earlier (TB_); a word outside the pool reads block 0 of the slab
+    // instead (no address is formed from it) and the key is masked at use (bit u of OK_).  Behind the loads, the words of the batch after next.
+#define FD_LOAD(KB_, VB_, MB_, TB_, OK_, t_)                                                                            \
     _Pragma("unroll") for (int u = 0; u < U; ++u) {                                                                  \
         int j_ = grp + ((t_) * U + u) * KPB;                                                                         \
         j_ = j_ < pos ? j_ : last;                                                                                   \
-        const unsigned off_ = (unsigned)(j_ * D * ESZ + c * 16);                                                     \
+        int r_ = j_;                                                                                                 \
+        if constexpr (PAGED) {                                                                                       \
+            const bool v_ = (unsigned)TB_[u] < (unsigned)pg.n_blocks;                                                \
+            OK_ = u == 0 ? (int)v_ : OK_ | ((int)v_ << u);                                                           \
+            r_ = (v_ ? TB_[u] * VCLA_KV_BLOCK_ROWS : 0) + (j_ & (VCLA_KV_BLOCK_ROWS - 1));                           \
+        }                                                                                                            \
+        const unsigned off_ = (unsigned)(r_ * D * ESZ + c * 16);                                                     \
         KB_[u] = __builtin_bit_cast(u32x4_t, __builtin_amdgcn_raw_buffer_load_b128(rK, off_, 0, 2 /* nt */));         \
         VB_[u] = __builtin_bit_cast(u32x4_t, __builtin_amdgcn_raw_buffer_load_b128(rV, off_, 0, 2 /* nt */));         \
         MB_[u] = MASK ? km[j_] : 1;                                                                                  \
     }                                                                                                                \
+    FD_TABLE(TB_, (t_) + 2)                                                                                          \
     __builtin_amdgcn_sched_barrier(0);
     const int nb = (pos + U * KPB - 1) / (U * KPB);          // batches of U keys per lane group (workgroup-uniform)
     if (nb > 0) {            // the first TWO batches go out ahead of the RoPE arithmetic
-        FD_LOAD(kA, vA, mA, 0)
-        FD_LOAD(kB, vB, mB, 1)
+        FD_TABLE(tA, 0)
+        FD_TABLE(tB, 1)
+        FD_LOAD(kA, vA, mA, tA, okA, 0)
+        FD_LOAD(kB, vB, mB, tB, okB, 1)
     }
     if constexpr (QP) {
         if (tid < HALF) {     // what the GEMM epilogue + reduce would have stored: (slice 0 + slice 1) * rstd * w_scale, rounded to bf16
@@ -495,8 +569,10 @@ __global__ __launch_bounds__(NW * 64, NW == 2 ? 4 : 2) void attn_decode_flash_ke
             kbase[(int64_t)pos * D + tid + HALF] = f32_to_fp8(r1);
         } else {
             knew[tid] = r0; knew[tid + HALF] = r1;
-            reinterpret_cast<bf16_t*>(kbase)[(int64_t)pos * D + tid] = f2bf(r0);
-            reinterpret_cast<bf16_t*>(kbase)[(int64_t)pos * D + tid + HALF] = f2bf(r1);
+            if (!PAGED || arow >= 0) {
+                reinterpret_cast<bf16_t*>(kbase)[(int64_t)arow * D + tid] = f2bf(r0);
+                reinterpret_cast<bf16_t*>(kbase)[(int64_t)arow * D + tid + HALF] = f2bf(r1);
+            }
         }
     } else {
         for (int i = tid - HALF; i < D; i += NT - HALF) {    // the threads past the RoPE lanes move the value row
@@ -512,7 +588,7 @@ __global__ __launch_bounds__(NW * 64, NW == 2 ? 4 : 2) void attn_decode_flash_ke
                 vbase[(int64_t)pos * D + i] = f32_to_fp8(bf2f(v));
             } else {
                 vnew[i] = bf2f(v);
-                reinterpret_cast<bf16_t*>(vbase)[(int64_t)pos * D + i] = v;
+                if (!PAGED || arow >= 0) reinterpret_cast<bf16_t*>(vbase)[(int64_t)arow * D + i] = v;
             }
         }
     }
@@ -521,7 +597,14 @@ __global__ __launch_bounds__(NW * 64, NW == 2 ? 4 : 2) void attn_decode_flash_ke
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-    const u32x4_t qv = *reinterpret_cast<const u32x4_t*>(qpk + c * (E / 2));      // this lane's first 8 q values, packed bf16
+    u32x4_t qv = *reinterpret_cast<const u32x4_t*>(qpk + c * (E / 2));            // this lane's first 8 q values, packed bf16
+    if constexpr (PAGED) {
+        // the LDS read is consumed HERE, in front of the loop: otherwise the compiler's one wait for it sits at the loop head as
+        // lgkmcnt(0), which on every trip also waits for the scalar table loads issued at the end of the trip before
+        uint32_t q0_ = qv.x;
+        asm volatile("v_mov_b32 %0, %0" : "+v"(q0_));
+        qv.x = q0_;
+    }
     u32x4_t qv1 = qv;                                                             // KV8: values 8 .. 15 of the chunk
     if constexpr (KV8) qv1 = *reinterpret_cast<const u32x4_t*>(qpk + c * (E / 2) + 4);
     const float sl2 = scale * 1.44269504088896340736f;                     // scores live in the log2 domain
@@ -529,14 +612,14 @@ __global__ __launch_bounds__(NW * 64, NW == 2 ? 4 : 2) void attn_decode_flash_ke
     float m_run = -INFINITY, l_run = 0.f, o[E];
 #pragma unroll
     for (int e = 0; e < E; ++e) o[e] = 0.f;
-#define FD_COMPUTE(KB_, VB_, MB_, t_)                                                                                \
+#define FD_COMPUTE(KB_, VB_, MB_, OK_, t_)                                                                              \
     {                                                                                                                \
         float s_[U];                                                                                                 \
         float mb_ = -INFINITY;                                                                                       \
         _Pragma("unroll") for (int u = 0; u < U; ++u) {                                                              \
             const int j_ = grp + ((t_) * U + u) * KPB;                                                               \
             const float d_ = group_sum<LPK>(KV8 ? dot16_fp8(qv, qv1, KB_[u]) : dot8_bf16(qv, KB_[u]));               \
-            s_[u] = (j_ < pos && MB_[u] != 0) ? d_ * sl2 : -INFINITY;                                                \
+            s_[u] = (j_ < pos && MB_[u] != 0 && (!PAGED || ((OK_ >> u) & 1))) ? d_ * sl2 : -INFINITY;                          \
             mb_ = fmaxf(mb_, s_[u]);                                                                                 \
         }                                                                                                            \
         const float mn_ = fmaxf(m_run, mb_);                                                                         \
@@ -559,12 +642,13 @@ __global__ __launch_bounds__(NW * 64, NW == 2 ? 4 : 2) void attn_decode_flash_ke
     // two batches per trip, both computed unconditionally (a batch past the context is all masked: p = 0, alpha = 1): a branch
     // around the second compute lets the compiler sink the B loads into it, right in front of their use -- no prefetch left
     for (int t = 0; t < nb; t += 2) {
-        FD_COMPUTE(kA, vA, mA, t)
-        FD_LOAD(kA, vA, mA, t + 2)                 // (rows past the context: a harmless re-load of the last row)
-        FD_COMPUTE(kB, vB, mB, t + 1)
-        FD_LOAD(kB, vB, mB, t + 3)
+        FD_COMPUTE(kA, vA, mA, okA, t)
+        FD_LOAD(kA, vA, mA, tA, okA, t + 2)        // (rows past the context: a harmless re-load of the last row)
+        FD_COMPUTE(kB, vB, mB, okB, t + 1)
+        FD_LOAD(kB, vB, mB, tB, okB, t + 3)
     }
 #undef FD_LOAD
+#undef FD_TABLE
 #undef FD_COMPUTE
     {   // the new token (key / value still in LDS): every group computes it, only group 0 of the workgroup folds it in
         float d_ = 0.f;
@@ -632,13 +716,15 @@ __global__ __launch_bounds__(NW * 64, NW == 2 ? 4 : 2) void attn_decode_flash_ke
 template <typename T, int D>
 static int launch_decode(const void* qkv, void* kc, void* vc, const float* cos_tab, const float* sin_tab, void* out, int B,
                          int H, int ctx_max, int pos0, const int32_t* pos_dev, const int32_t* key_mask, int64_t key_mask_ld,
-                         float scale, int out_frag, hipStream_t s, bool kv8 = false, const QkvParts* qp = nullptr, bool rows = false) {
+                         float scale, int out_frag, hipStream_t s, bool kv8 = false, const QkvParts* qp = nullptr, bool rows = false,
+                         const KvPages* pages = nullptr) {
     const int sc_cap = (ctx_max + 63) & ~63;
     // batch form: 2-wave workgroups (8 per CU: one round for B * H <= 2048) while the context is short enough that the extra
     // passes over K and V (64 instead of 128 rows per pass) cost less than the second round of workgroups saves
     // (measured at B = 64, H = 32, context 192: 46.0 -> 42.4 us per launch against the 4-wave form)
     const int NWs = (D == 128 && (int64_t)B * H >= 1024) ? 2 : 4;
-    const size_t lds = (size_t)(3 * D + 2 * NWs + NWs * D + sc_cap) * sizeof(float);
+    // paged: behind the scores, one word per block of the logical cap (the sequence's row of the table)
+    const size_t lds = (size_t)(3 * D + 2 * NWs + NWs * D + sc_cap + (pages ? sc_cap / VCLA_KV_BLOCK_ROWS : 0)) * sizeof(float);
     VCLA_REQUIRE(lds <= 64 * 1024, VCLA_ERR_BAD_SHAPE, "attn_decode: ctx_max=%d needs %zu B of LDS (max 64 KiB)", ctx_max, lds);
     dim3 grid(H, B);
     const int out_frag_mt = out_frag ? (B + 15) / 16 : 0;
@@ -658,6 +744,22 @@ static int launch_decode(const void* qkv, void* kc, void* vc, const float* cos_t
         label = DEC_LBL("attn_decode_flash_kernel<D=", ",NW=" #NW_ ",MASK=" #MASK_ ",KV8=" #KV8_ ",QP=false,ROWS=" #ROWS_ ">");                             \
     } while (0)
         VCLA_REQUIRE(!rows || (!qp && !kv8), VCLA_ERR_BAD_ARG, "attn_decode: per-row positions go with the bf16 cache and the plain qkv row");
+        if (flash_ok && pages) {   // the pool behind a block table: the per-row form with the address map (head dim 64 / 128, checked by the entry)
+            if constexpr (D >= 64) {
+#define FD_GOG(NW_, MASK_)                                                                                                                                   \
+    do {                                                                                                                                                    \
+        attn_decode_flash_kernel<D, NW_, MASK_, false, false, true, true><<<grid, NW_ * 64, 0, s>>>(qkv, kc, vc, cos_tab, sin_tab, (bf16_t*)out, H, ctx_max, \
+                                                                                                    pos0, pos_dev, key_mask, key_mask_ld, scale,            \
+                                                                                                    out_frag_mt, QkvParts{}, *pages);                       \
+        label = DEC_LBL("attn_decode_flash_kernel<D=", ",NW=" #NW_ ",MASK=" #MASK_ ",KV8=false,QP=false,ROWS=true,PAGED=true>");                            \
+    } while (0)
+                if (small_wg) { if (key_mask) FD_GOG(2, true); else FD_GOG(2, false); }
+                else { if (key_mask) FD_GOG(4, true); else FD_GOG(4, false); }
+#undef FD_GOG
+                VCLA_CHECK_LAUNCH(label);
+                return VCLA_OK;
+            }
+        }
         if (qp) {    // q / k / v arrive as two raw fp32 K slices of the qkv projection: 2-wave form only (batch decode, B * H >= 1024)
             if constexpr (D >= 64) {
                 VCLA_REQUIRE(flash_ok && small_wg, VCLA_ERR_BAD_ARG, "attn_decode: the split-qkv form needs B * H >= 1024 and a 16-byte aligned output");
@@ -710,7 +812,22 @@ static int launch_decode(const void* qkv, void* kc, void* vc, const float* cos_t
         label = sizeof(T) == 2 ? DEC_LBL("attn_decode_kernel<bf16,D=", ",COOP=" #COOP_ ",NW=" #NW_ ",ROWS=" #ROWS_ ">")                                     \
                                : DEC_LBL("attn_decode_kernel<f32,D=", ",COOP=" #COOP_ ",NW=" #NW_ ",ROWS=" #ROWS_ ">");                                      \
     } while (0)
-    if (rows) {
+    if (pages) {
+        if constexpr (D >= 64) {
+#define PD_GOG(COOP_, NW_)                                                                                                                                  \
+    do {                                                                                                                                                    \
+        attn_decode_kernel<T, D, COOP_, NW_, true, true><<<grid, NW_ * 64, lds, s>>>((const T*)qkv, (T*)kc, (T*)vc, cos_tab, sin_tab, (T*)out, H, ctx_max,   \
+                                                                                     pos0, pos_dev, key_mask, key_mask_ld, scale, sc_cap, out_frag_mt,      \
+                                                                                     *pages);                                                               \
+        label = sizeof(T) == 2 ? DEC_LBL("attn_decode_kernel<bf16,D=", ",COOP=" #COOP_ ",NW=" #NW_ ",ROWS=true,PAGED=true>")                                \
+                               : DEC_LBL("attn_decode_kernel<f32,D=", ",COOP=" #COOP_ ",NW=" #NW_ ",ROWS=true,PAGED=true>");                                 \
+    } while (0)
+            if (coop && NWs == 2) PD_GOG(true, 2);
+            else if (coop) PD_GOG(true, 4);
+            else PD_GOG(false, 4);
+#undef PD_GOG
+        }
+    } else if (rows) {
         if (coop && NWs == 2) PD_GO(true, 2, true);
         else if (coop) PD_GO(true, 4, true);
         else PD_GO(false, 4, true);
@@ -727,7 +844,7 @@ static int launch_decode(const void* qkv, void* kc, void* vc, const float* cos_t
 
 static int attn_decode_entry(const void* qkv, void* k_cache, void* v_cache, const float* cos_tab, const float* sin_tab, void* out, int B, int H, int d,
                              int ctx_max, int pos0, const int32_t* pos_dev, const int32_t* key_mask, int64_t key_mask_ld, float scale, int dtype, int out_frag,
-                             void* stream, const QkvParts* qp, bool rows = false);
+                             void* stream, const QkvParts* qp, bool rows = false, const KvPages* pages = nullptr);
 
 extern "C" int vcla_attn_decode_fused_parts(const float* qkv_parts, int64_t slice_stride, const float* row_ssq, const float* w_scale, float norm_eps,
                                             void* k_cache, void* v_cache, const float* cos_tab, const float* sin_tab, void* out, int B, int H, int d,
@@ -762,10 +879,32 @@ extern "C" int vcla_attn_decode_rows(const void* qkv, void* k_cache, void* v_cac
                              nullptr, /*rows=*/true);
 }
 
+// The per-row form over a pool of 16-row blocks [H][n_blocks * 16][d] behind the block table `pages` (device memory, [B][ld], -1 = none):
+// ctx_cap is the logical cap of a sequence, only addresses take the pool.  The caller validates the table; the kernels never form an
+// address from an entry outside [0, n_blocks).
+extern "C" int vcla_attn_decode_paged(const void* qkv, void* k_pool, void* v_pool, const float* cos_tab, const float* sin_tab, void* out, int B, int H,
+                                      int d, int ctx_cap, const int32_t* row_pos, const vcla_kv_pages* pages, const int32_t* key_mask, int64_t key_mask_ld,
+                                      float scale, int dtype, int out_frag, void* stream) {
+    VCLA_KNOBS_SCOPE();
+    VCLA_REQUIRE(row_pos, VCLA_ERR_BAD_ARG, "attn_decode_paged: row_pos is NULL");
+    VCLA_REQUIRE(!(dtype & VCLA_KV_FP8), VCLA_ERR_BAD_DTYPE, "attn_decode_paged: the e4m3 K/V cache is not supported");
+    VCLA_REQUIRE(pages && pages->table && pages->n_blocks >= 1, VCLA_ERR_BAD_ARG, "attn_decode_paged: a null block table, or an empty pool");
+    VCLA_REQUIRE(d == 64 || d == 128, VCLA_ERR_BAD_SHAPE, "attn_decode_paged: head dim %d not in {64,128}", d);
+    VCLA_REQUIRE(ctx_cap > 0 && (int64_t)pages->ld * VCLA_KV_BLOCK_ROWS >= ctx_cap, VCLA_ERR_BAD_SHAPE,
+                 "attn_decode_paged: a table row of %d blocks does not cover ctx_cap %d", pages->ld, ctx_cap);
+    // a head's slab is one buffer descriptor plus a 32-bit byte offset
+    VCLA_REQUIRE((int64_t)pages->n_blocks * VCLA_KV_BLOCK_ROWS * d * ((dtype & ~VCLA_KV_FP8) == VCLA_F32 ? 4 : 2) < ((int64_t)1 << 32), VCLA_ERR_BAD_SHAPE,
+                 "attn_decode_paged: n_blocks=%d: a head's slab must stay below 4 GiB", pages->n_blocks);
+    VCLA_REQUIRE(!key_mask || key_mask_ld >= ctx_cap, VCLA_ERR_BAD_ARG, "attn_decode_paged: key_mask_ld %lld < ctx_cap %d", (long long)key_mask_ld, ctx_cap);
+    const KvPages pg{pages->table, pages->ld, pages->n_blocks};
+    return attn_decode_entry(qkv, k_pool, v_pool, cos_tab, sin_tab, out, B, H, d, ctx_cap, 0, row_pos, key_mask, key_mask_ld, scale, dtype, out_frag, stream,
+                             nullptr, /*rows=*/true, &pg);
+}
+
 static int attn_decode_entry(const void* qkv, void* k_cache, void* v_cache, const float* cos_tab,
                              const float* sin_tab, void* out, int B, int H, int d, int ctx_max, int pos0,
                              const int32_t* pos_dev, const int32_t* key_mask, int64_t key_mask_ld, float scale,
-                             int dtype, int out_frag, void* stream, const QkvParts* qp, bool rows) {
+                             int dtype, int out_frag, void* stream, const QkvParts* qp, bool rows, const KvPages* pages) {
     const bool kv8 = (dtype & VCLA_KV_FP8) != 0;
     dtype &= ~VCLA_KV_FP8;
     VCLA_REQUIRE(dtype == VCLA_F32 || dtype == VCLA_BF16, VCLA_ERR_BAD_DTYPE, "attn_decode: bad dtype %d", dtype);
@@ -780,7 +919,7 @@ static int attn_decode_entry(const void* qkv, void* k_cache, void* v_cache, cons
                  "attn_decode: out_frag needs bf16, B <= 64 (got %d) and H*d %% 32 == 0", B);
     if (B == 0) return VCLA_OK;
     hipStream_t s = (hipStream_t)stream;
-#define DEC_CASE(TT, DD) return launch_decode<TT, DD>(qkv, k_cache, v_cache, cos_tab, sin_tab, out, B, H, ctx_max, pos0, pos_dev, key_mask, key_mask_ld, scale, out_frag, s, kv8, qp, rows)
+#define DEC_CASE(TT, DD) return launch_decode<TT, DD>(qkv, k_cache, v_cache, cos_tab, sin_tab, out, B, H, ctx_max, pos0, pos_dev, key_mask, key_mask_ld, scale, out_frag, s, kv8, qp, rows, pages)
     if (dtype == VCLA_F32) {
         if (d == 32) DEC_CASE(float, 32);
         if (d == 64) DEC_CASE(float, 64);

@@ -205,6 +205,8 @@ struct vcla_ctx {
         int rows_n = 0;
         int cache_seqs = 0;
         bool rows_lists_ready = false;   // the scratch holds the work list of rows_seqs (written by the first layer of the pass)
+        // inside vcla_llama_decode_slots_paged: kv_cache is a pool [L][2][H][n_blocks * 16][d] behind this block table, ctx_max the logical cap
+        const vcla_kv_pages* pages = nullptr;
     } run;
     // cached graphs of the vision stack and of the prefill (~250 / ~290 launches, host-bound at B = 1; run_macro), two shapes in rotation
     // each (e.g. forward(all_logits) and generate()'s prefill, or two batch sizes); of one decode step and of one verify iteration
@@ -526,6 +528,11 @@ extern "C" size_t vcla_llama_workspace_bytes(const vcla_ctx* ctx, int B, int T) 
     if (!ctx || B <= 0 || T <= 0) return 0;
     return carve_llama(ctx, B, T, nullptr, nullptr);
 }
+extern "C" size_t vcla_kv_pool_bytes(const vcla_ctx* ctx, int n_blocks) {
+    if (!ctx || n_blocks <= 0) return 0;
+    return (size_t)ctx->c.t_layers * 2 * ctx->c.t_hidden * (size_t)n_blocks * VCLA_KV_BLOCK_ROWS * esz(ctx);
+}
+
 extern "C" size_t vcla_kv_cache_bytes(const vcla_ctx* ctx, int B, int ctx_max) {
     if (!ctx || B <= 0 || ctx_max <= 0) return 0;
     return (size_t)ctx->c.t_layers * 2 * B * ctx->c.t_hidden * (size_t)ctx_max * (ctx->c.t_kv_fp8 ? 1 : esz(ctx));   // t_kv_fp8: e4m3 bytes
@@ -818,7 +825,10 @@ static int llama_layer(vcla_ctx* ctx, hipStream_t s, const LlamaLayer& L, const 
     const int D = c.t_hidden, H = c.t_heads, d = D / H, M = B * T;
     const bool kv8 = c.t_kv_fp8 != 0;                   // e4m3 cache rows (bf16 activations; checked at ctx creation)
     const int dkv = dt | (kv8 ? VCLA_KV_FP8 : 0);
-    const size_t per = (size_t)(ctx->run.cache_seqs > 0 ? ctx->run.cache_seqs : B) * H * ctx_max * d * (kv8 ? 1 : e);  // bytes of one K (or V) slab of one layer
+    const vcla_kv_pages* pages = ctx->run.pages;
+    // bytes of one K (or V) slab of one layer; paged: the pool is ONE sequence of n_blocks * 16 rows
+    const size_t per = pages ? (size_t)H * pages->n_blocks * VCLA_KV_BLOCK_ROWS * d * e
+                             : (size_t)(ctx->run.cache_seqs > 0 ? ctx->run.cache_seqs : B) * H * ctx_max * d * (kv8 ? 1 : e);
     char* kc = (char*)kv_cache + (size_t)(2 * l) * per;
     char* vc = kc + per;
     // 2 <= M <= 64 decode rows with fragment-major weight copies: the streaming GEMMs (gemm_stream.hip).  Every operand is
@@ -854,8 +864,12 @@ static int llama_layer(vcla_ctx* ctx, hipStream_t s, const LlamaLayer& L, const 
             // a slots step (vcla_llama_decode_slots): every row at its own position; the plain qkv projection (the split form has no per-row variant)
             RUN(gemm_ds(ctx, s, w.h, L.wqkv, L.vqkv, nullptr, 0, w.qkv, 3 * D, nullptr, M, 3 * D, D, VCLA_EPI_NONE, 0,
                         a_def ? w.ssq : nullptr, a_def ? ctx->run.ssq_parts : 0));
-            RUN(vcla_attn_decode_rows(w.qkv, kc, vc, ctx->rope_cos, ctx->rope_sin, w.ao, B, H, d, ctx_max, row_pos, key_mask, ctx_max, scale_, dt,
-                                      /*out_frag=*/1, s));
+            if (pages)
+                RUN(vcla_attn_decode_paged(w.qkv, kc, vc, ctx->rope_cos, ctx->rope_sin, w.ao, B, H, d, ctx_max, row_pos, pages, key_mask, ctx_max, scale_, dt,
+                                           /*out_frag=*/1, s));
+            else
+                RUN(vcla_attn_decode_rows(w.qkv, kc, vc, ctx->rope_cos, ctx->rope_sin, w.ao, B, H, d, ctx_max, row_pos, key_mask, ctx_max, scale_, dt,
+                                          /*out_frag=*/1, s));
         } else if (ctx->run.rows_seqs) {
             // ragged admission: the T packed rows are the blocks of several slots, each at its own position
             RUN(gemm_ds(ctx, s, w.h, L.wqkv, L.vqkv, nullptr, 0, w.qkv, 3 * D, nullptr, M, 3 * D, D, VCLA_EPI_NONE, 0,
@@ -927,7 +941,8 @@ static int llama_layer(vcla_ctx* ctx, hipStream_t s, const LlamaLayer& L, const 
                              ctx->run.extend_scratch_bytes, s));
     } else if (T == 1 && row_pos) {
         // a slots step: the same launch with one position per row
-        RUN(vcla_attn_decode_rows(w.qkv, kc, vc, ctx->rope_cos, ctx->rope_sin, w.ao, B, H, d, ctx_max, row_pos, key_mask, ctx_max, scale, dt, 0, s));
+        if (pages) RUN(vcla_attn_decode_paged(w.qkv, kc, vc, ctx->rope_cos, ctx->rope_sin, w.ao, B, H, d, ctx_max, row_pos, pages, key_mask, ctx_max, scale, dt, 0, s));
+        else RUN(vcla_attn_decode_rows(w.qkv, kc, vc, ctx->rope_cos, ctx->rope_sin, w.ao, B, H, d, ctx_max, row_pos, key_mask, ctx_max, scale, dt, 0, s));
     } else if (T == 1) {
         // decode: RoPE + KV append + attention over the cache in one launch
         RUN(vcla_attn_decode_fused(w.qkv, kc, vc, ctx->rope_cos, ctx->rope_sin, w.ao, B, H, d, ctx_max, pos0, pos_dev, key_mask,
@@ -1430,10 +1445,12 @@ extern "C" int vcla_llama_verify_loop(vcla_ctx* ctx, const vcla_lookup_args* arg
 // with logprobs the copy, which the stats pass then writes on the argmax path too -- and the transition on the ids taken.  Part of the graph key.
 // stops (vcla_llama_decode_slots_stops, csrc/slots.hip): per-slot stop sequences in device memory, decided by the bookkeeping launch.  Null: the
 // launches and the graph key of the entry without them; otherwise the table pointer extends the key.
-extern "C" int vcla_llama_decode_slots_stops(vcla_ctx* ctx, const vcla_slot_args* slots, int n_steps, void* kv_cache, int ctx_max,
-                                             const int32_t* key_mask, void* ws, size_t ws_bytes, int use_graph, const vcla_sample_args* sampling,
-                                             const int32_t* eos_rows, const vcla_sample_row* rows, const vcla_logprob_args* logprobs,
-                                             const vcla_constrain_args* constraints, const vcla_stop_args* stops, void* stream) {
+// pages (vcla_llama_decode_slots_paged): kv_cache is a pool of 16-row blocks behind a block table in device memory, ctx_max the logical cap of a
+// slot.  Null: the launches and the graph key of the entry without it; otherwise the struct extends the key.
+static int decode_slots_impl(vcla_ctx* ctx, const vcla_slot_args* slots, int n_steps, void* kv_cache, int ctx_max,
+                             const int32_t* key_mask, void* ws, size_t ws_bytes, int use_graph, const vcla_sample_args* sampling,
+                             const int32_t* eos_rows, const vcla_sample_row* rows, const vcla_logprob_args* logprobs,
+                             const vcla_constrain_args* constraints, const vcla_stop_args* stops, const vcla_kv_pages* pages, void* stream) {
     VCLA_KNOBS_SCOPE();
     VCLA_REQUIRE(ctx && ctx->finalized && ctx->c.t_layers > 0, VCLA_ERR_BAD_ARG, "llama_decode_slots: context not finalized, or vision-only");
     RUN(slot_args_check(slots, "llama_decode_slots"));
@@ -1473,6 +1490,12 @@ extern "C" int vcla_llama_decode_slots_stops(vcla_ctx* ctx, const vcla_slot_args
                      c.t_vocab, VCLA_CS_MAX_VOCAB);
     }
     VCLA_REQUIRE(!stops || stops->seqs, VCLA_ERR_BAD_ARG, "llama_decode_slots_stops: a null stop table");
+    if (pages) {
+        const int hd = c.t_hidden / c.t_heads;
+        VCLA_REQUIRE(pages->table && pages->n_blocks >= 1 && (int64_t)pages->ld * VCLA_KV_BLOCK_ROWS >= ctx_max, VCLA_ERR_BAD_ARG,
+                     "llama_decode_slots_paged: a null block table, an empty pool, or a table row of %d blocks under ctx_max %d", pages->ld, ctx_max);
+        VCLA_REQUIRE(hd == 64 || hd == 128, VCLA_ERR_BAD_SHAPE, "llama_decode_slots_paged: head dim %d not in {64,128}", hd);
+    }
     if (n_steps == 0) return VCLA_OK;
     hipStream_t s = (hipStream_t)stream;
     LlamaWs w;
@@ -1483,6 +1506,7 @@ extern "C" int vcla_llama_decode_slots_stops(vcla_ctx* ctx, const vcla_slot_args
     auto one_step = [&](hipStream_t st) -> int {
         const RunScope scope(ctx);
         ctx->run.decode_step = true;
+        ctx->run.pages = pages;
         RUN(decoder_rows(ctx, st, w, B, 1, 0, nullptr, kv_cache, ctx_max, key_mask, w.logits, slots->row_pos));
         if (logprobs) RUN(vcla_logprob_rows(w.logits, c.t_vocab, B, c.t_vocab, slots->hist_len, slots->hist_cap, logprobs, lp_lse, lp_copy, c.t_vocab, st));
         float* sel = lp_copy ? lp_copy : w.logits;   // the row the selector reads
@@ -1495,8 +1519,10 @@ extern "C" int vcla_llama_decode_slots_stops(vcla_ctx* ctx, const vcla_slot_args
     };
     struct Key { const void *kv_cache, *key_mask, *ws, *eos_rows, *rows; int ctx_max, has_samp; vcla_slot_args slots; vcla_sample_args samp;
                  int has_lp; vcla_logprob_args lp; int has_cs; vcla_constrain_args cs; };
-    struct { Key k; const void* stop_seqs; } key_stops;   // with a stop table: the key without one, then the table pointer
-    memset(&key_stops, 0, sizeof key_stops);
+    struct KeyStops { Key k; const void* stop_seqs; };   // with a stop table: the key without one, then the table pointer
+    struct { KeyStops ks; const void* table; int ld, n_blocks; } key_pages;   // with a block table: the key with a stop table (null or not), then the struct
+    memset(&key_pages, 0, sizeof key_pages);
+    KeyStops& key_stops = key_pages.ks;
     Key& key = key_stops.k;
     key.kv_cache = kv_cache; key.key_mask = key_mask; key.ws = ws; key.ctx_max = ctx_max; key.has_samp = sampling != nullptr;
     key.eos_rows = eos_rows; key.rows = rows;
@@ -1506,9 +1532,27 @@ extern "C" int vcla_llama_decode_slots_stops(vcla_ctx* ctx, const vcla_slot_args
     if (logprobs) memcpy(&key.lp, logprobs, sizeof(*logprobs));
     key.has_cs = constraints != nullptr;
     if (constraints) memcpy(&key.cs, constraints, sizeof(*constraints));
-    if (!stops) return run_steps(ctx->slots_graph, "slots", key, use_graph, n_steps, s, one_step);
-    key_stops.stop_seqs = stops->seqs;
-    return run_steps(ctx->slots_graph, "slots", key_stops, use_graph, n_steps, s, one_step);
+    if (!stops && !pages) return run_steps(ctx->slots_graph, "slots", key, use_graph, n_steps, s, one_step);
+    if (stops) key_stops.stop_seqs = stops->seqs;
+    if (!pages) return run_steps(ctx->slots_graph, "slots", key_stops, use_graph, n_steps, s, one_step);
+    key_pages.table = pages->table; key_pages.ld = pages->ld; key_pages.n_blocks = pages->n_blocks;
+    return run_steps(ctx->slots_graph, "slots", key_pages, use_graph, n_steps, s, one_step);
+}
+
+extern "C" int vcla_llama_decode_slots_stops(vcla_ctx* ctx, const vcla_slot_args* slots, int n_steps, void* kv_cache, int ctx_max,
+                                             const int32_t* key_mask, void* ws, size_t ws_bytes, int use_graph, const vcla_sample_args* sampling,
+                                             const int32_t* eos_rows, const vcla_sample_row* rows, const vcla_logprob_args* logprobs,
+                                             const vcla_constrain_args* constraints, const vcla_stop_args* stops, void* stream) {
+    return decode_slots_impl(ctx, slots, n_steps, kv_cache, ctx_max, key_mask, ws, ws_bytes, use_graph, sampling, eos_rows, rows, logprobs, constraints, stops,
+                             nullptr, stream);
+}
+
+extern "C" int vcla_llama_decode_slots_paged(vcla_ctx* ctx, const vcla_slot_args* slots, int n_steps, void* kv_cache, int ctx_max,
+                                             const int32_t* key_mask, void* ws, size_t ws_bytes, int use_graph, const vcla_sample_args* sampling,
+                                             const int32_t* eos_rows, const vcla_sample_row* rows, const vcla_logprob_args* logprobs,
+                                             const vcla_constrain_args* constraints, const vcla_stop_args* stops, const vcla_kv_pages* pages, void* stream) {
+    return decode_slots_impl(ctx, slots, n_steps, kv_cache, ctx_max, key_mask, ws, ws_bytes, use_graph, sampling, eos_rows, rows, logprobs, constraints, stops,
+                             pages, stream);
 }
 
 extern "C" int vcla_llama_decode_slots_constrained(vcla_ctx* ctx, const vcla_slot_args* slots, int n_steps, void* kv_cache, int ctx_max,

@@ -239,6 +239,43 @@ def kv_block_table(entries, n_blocks: int, B_slots: int, ctx_max: int, to_pool: 
     return torch.tensor([[int(b), int(s), int(r)] for b, s, r in entries], dtype=torch.int32).view(-1, 3)
 
 
+class KvPages(C.Structure):
+    """vcla_kv_pages: the block table of a paged K/V pool, in device memory"""
+    _fields_ = [("table", C.c_void_p), ("ld", C.c_int), ("n_blocks", C.c_int)]
+
+
+def kv_pages(table: torch.Tensor, n_blocks: int) -> KvPages:
+    """vcla_kv_pages over the device table int32 [B, ld]; the struct holds a bare pointer: the tensor must stay alive"""
+    if table.dtype != torch.int32 or table.dim() != 2 or not table.is_contiguous():
+        raise ValueError("kv_pages: the table must be a contiguous int32 [B, ld] tensor")
+    a = KvPages()
+    a.table, a.ld, a.n_blocks = table.data_ptr(), int(table.shape[1]), int(n_blocks)
+    return a
+
+
+def kv_page_rows(rows, rows_needed, n_blocks: int, ld: int, owned=()) -> torch.Tensor:
+    """per-slot block lists -> int32 host tensor [len(rows), ld], every row its blocks in logical order and -1 behind them (rows of the
+    table of vcla_attn_decode_paged).  The launcher cannot check a table in device memory: entries inside [0, n_blocks), no block owned
+    twice -- among these rows or with `owned`, the blocks of the slots that stay live -- and enough blocks for the rows_needed[k] rows
+    slot k will write are checked HERE, before the upload; ValueError names the row."""
+    out = torch.full((len(rows), ld), -1, dtype=torch.int32)
+    seen = set(int(b) for b in owned)
+    for k, (blocks, need) in enumerate(zip(rows, rows_needed)):
+        blocks = [int(b) for b in blocks]
+        if len(blocks) > ld:
+            raise ValueError(f"kv table row {k}: {len(blocks)} blocks for a table of {ld} per slot")
+        if len(blocks) * KV_BLOCK_ROWS < int(need):
+            raise ValueError(f"kv table row {k}: {len(blocks)} blocks of {KV_BLOCK_ROWS} rows for the {int(need)} rows the slot will write")
+        for b in blocks:
+            if not 0 <= b < n_blocks:
+                raise ValueError(f"kv table row {k}: block {b} outside the pool of {n_blocks}")
+            if b in seen:
+                raise ValueError(f"kv table row {k}: block {b} is owned twice")
+            seen.add(b)
+        out[k, :len(blocks)] = torch.tensor(blocks, dtype=torch.int32)
+    return out
+
+
 SLOT_MAX_EOS = 8            # VCLA_SLOT_MAX_EOS
 SLOT_SUMMARY_WORDS = 4      # VCLA_SLOT_SUMMARY_WORDS: slots still active, the launch's arrival counter, two reserved words
 
@@ -431,6 +468,10 @@ SYMBOLS = {
     "vcla_slot_step_stops": (_i, [_vp, C.POINTER(SlotArgs), _vp, C.POINTER(StopArgs), _vp, _vp, _i, _i, _i, _vp]),
     "vcla_llama_decode_slots_stops": (_i, [_vp, C.POINTER(SlotArgs), _i, _vp, _i, _vp, _vp, _sz, _i, C.POINTER(SampleArgs), _vp, _vp,
                                            C.POINTER(LogprobArgs), C.POINTER(ConstrainArgs), C.POINTER(StopArgs), _vp]),
+    "vcla_kv_pool_bytes": (_sz, [_vp, _i]),
+    "vcla_attn_decode_paged": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, C.POINTER(KvPages), _vp, _i64, _f, _i, _i, _vp]),
+    "vcla_llama_decode_slots_paged": (_i, [_vp, C.POINTER(SlotArgs), _i, _vp, _i, _vp, _vp, _sz, _i, C.POINTER(SampleArgs), _vp, _vp,
+                                           C.POINTER(LogprobArgs), C.POINTER(ConstrainArgs), C.POINTER(StopArgs), C.POINTER(KvPages), _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -67,6 +67,62 @@ def check_stop_sequences(requests_stops: Sequence, vocab_size: int, forced: Opti
     return out
 
 
+KV_BLOCK_ROWS = 16          # VCLA_KV_BLOCK_ROWS
+
+
+def check_kv_pool_tokens(kv_pool_tokens) -> Optional[int]:
+    """the `kv_pool_tokens` argument of generate_many / chat_many: None, or a positive int (bool is refused) -> blocks of the pool"""
+    if kv_pool_tokens is None:
+        return None
+    if isinstance(kv_pool_tokens, bool) or not isinstance(kv_pool_tokens, int) or kv_pool_tokens <= 0:
+        raise ValueError(f"kv_pool_tokens must be None or a positive integer (got {kv_pool_tokens!r})")
+    return (int(kv_pool_tokens) + KV_BLOCK_ROWS - 1) // KV_BLOCK_ROWS
+
+
+def blocks_for(rows: int) -> int:
+    """blocks of KV_BLOCK_ROWS rows that hold `rows` rows"""
+    return (int(rows) + KV_BLOCK_ROWS - 1) // KV_BLOCK_ROWS
+
+
+class KvBlockAllocator:
+    """The blocks 0 .. n_blocks - 1 of a paged K/V pool, host only: alloc(n) hands out n free blocks or None (and
+    then takes nothing), free(list) takes them back; a double free or a block that was never handed out raises.  used / peak count blocks."""
+
+    def __init__(self, n_blocks: int):
+        if isinstance(n_blocks, bool) or not isinstance(n_blocks, int) or n_blocks < 1:
+            raise ValueError(f"KvBlockAllocator: n_blocks must be a positive integer (got {n_blocks!r})")
+        self.n_blocks = n_blocks
+        self._free = list(range(n_blocks - 1, -1, -1))           # a stack: alloc pops from the end, a freed block is reused first
+        self._out = set()
+        self.peak = 0
+
+    @property
+    def used(self) -> int:
+        return len(self._out)
+
+    @property
+    def available(self) -> int:
+        return len(self._free)
+
+    def alloc(self, n: int):
+        if n < 0:
+            raise ValueError(f"KvBlockAllocator.alloc: n={n}")
+        if n > len(self._free):
+            return None
+        got = [self._free.pop() for _ in range(n)]
+        self._out.update(got)
+        self.peak = max(self.peak, len(self._out))
+        return got
+
+    def free(self, blocks) -> None:
+        blocks = [int(b) for b in blocks]
+        bad = [b for b in blocks if b not in self._out]
+        if bad or len(set(blocks)) != len(blocks):
+            raise ValueError(f"KvBlockAllocator.free: blocks {sorted(set(bad)) or blocks} are not allocated (a double free, or a block of another pool)")
+        self._out.difference_update(blocks)
+        self._free.extend(blocks)
+
+
 def stop_hit(tokens: Sequence[int], seqs) -> bool:
     """does the tail of `tokens` equal one of `seqs`?  (the brute-force statement of the stopping criterion)"""
     return any(len(q) <= len(tokens) and list(tokens[len(tokens) - len(q):]) == list(q) for q in (seqs or []) if len(q))
@@ -143,12 +199,22 @@ class InflightScheduler:
 
     stops[i] (lists of ids, or None): request i's stop sequences (checked by check_stop_sequences); the stepper decides them, the scheduler
     counts them.  Streaming: deliver() hands the tokens every running request produced since its last call to a callback, in ascending
-    request order, and returns the slots whose callback asked to cancel; cancel() finishes such a request with what was delivered."""
+    request order, and returns the slots whose callback asked to cancel; cancel() finishes such a request with what was delivered.
+
+    kv_pool_tokens (an int, or None: nothing changes): the slots share a paged K/V pool of ceil(n / 16) blocks of 16 rows (DESIGN.md section
+    7k).  A request RESERVES ceil((T_group + budget) / 16) blocks when it is admitted (blocks[i]) and returns them when it is harvested.
+    Requests are still taken in arrival order; request i is admitted at a boundary only if, after it joins its group (whose T may grow, which
+    raises every member's need), the blocks of all groups of the boundary fit the free ones -- otherwise admission ends there with i at
+    the head of the queue.  A request that alone needs more blocks than the pool holds is refused up front, so the head always fits once
+    no slot is live.  Not beside share_prefix."""
 
     def __init__(self, prompt_lens: Sequence[int], budgets: Sequence[int], has_image: Sequence[bool], max_batch: int,
                  max_position_embeddings: int, image_at_head: bool = False, steps_per_sync: int = 8, share_prefix: bool = False,
                  logprobs: Optional[int] = None, targets: Optional[Sequence[Optional[Sequence[int]]]] = None,
-                 stops: Optional[Sequence[Optional[Sequence[Sequence[int]]]]] = None):
+                 stops: Optional[Sequence[Optional[Sequence[Sequence[int]]]]] = None, kv_pool_tokens: Optional[int] = None):
+        pool_blocks = check_kv_pool_tokens(kv_pool_tokens)
+        if pool_blocks is not None and share_prefix:
+            raise ValueError("kv_pool_tokens with share_prefix=True (the ragged admission pass needs a paged vcla_attn_extend_rows)")
         if max_batch < 1:
             raise ValueError(f"max_batch must be at least 1 (got {max_batch})")
         if steps_per_sync < 1:
@@ -192,6 +258,17 @@ class InflightScheduler:
         self.first_ended: List[tuple] = []                       # streaming: (request, its only token) of requests their first token ended, not yet delivered
         self.stats = {"requests": self.n, "slots": self.slots, "steps": 0, "tokens": 0, "admission_groups": 0, "slot_steps_active": 0,
                       "slot_steps_total": 0, "stop_requests": sum(x is not None for x in self.stops), "stop_hits": 0, "cancelled": 0, "stream_calls": 0}
+        self.pool: Optional[KvBlockAllocator] = None
+        self.blocks: Dict[int, List[int]] = {}                   # paged: running request -> the pool blocks it reserved, in logical order
+        if pool_blocks is not None:
+            big = [i for i in range(self.n) if blocks_for(self.T[i] + self.budget[i]) > pool_blocks]
+            if big:
+                raise ValueError(f"kv_pool_tokens={kv_pool_tokens}: a pool of {pool_blocks} blocks of {KV_BLOCK_ROWS} rows cannot hold request "
+                                 + ", ".join(f"{i} ({self.T[i]} + {self.budget[i]} rows = {blocks_for(self.T[i] + self.budget[i])} blocks)" for i in big))
+            self.pool = KvBlockAllocator(pool_blocks)
+            self._waited = False                                 # this boundary is already counted in admission_waits_blocks
+            self._rows_reserved = 0
+            self.stats.update(kv_pool_blocks=pool_blocks, kv_blocks_peak=0, kv_rows_reserved_peak=0, admission_waits_blocks=0)
 
     # ------------------------------------------------------------------ admission
     def free_slots(self) -> List[int]:
@@ -208,16 +285,24 @@ class InflightScheduler:
     def admit(self, free_slots: Sequence[int]) -> List[Group]:
         """The next requests in arrival order, one per free slot, as the groups that are prefilled together."""
         groups: List[Group] = []
+        if self.pool is not None and self._waited and self.running:
+            return groups                                        # the head waits for blocks: admission of this boundary has ended
         for b in sorted(free_slots):
             if not self.queue:
                 break
             if self.slot_req[b] is not None:
                 raise ValueError(f"slot {b} still holds request {self.slot_req[b]}")
-            i = self.queue.popleft()
+            i = self.queue[0]
             if self.share_prefix:
                 g = groups[0] if groups else None                # T_i + budget_i <= ctx_max holds for every request by construction
             else:
                 g = next((g for g in groups if self._fits(g, i)), None)
+            if self.pool is not None and self._blocks_needed(groups, g, i) > self.pool.available:
+                if not self._waited:                             # a free slot stays empty: the head of the queue waits for blocks
+                    self.stats["admission_waits_blocks"] += 1
+                    self._waited = True
+                break
+            self.queue.popleft()
             if g is None:
                 g = Group(image=self.has_image[i], ragged=self.share_prefix)
                 groups.append(g)
@@ -229,8 +314,24 @@ class InflightScheduler:
         for g in groups:
             for i in g.requests:
                 self.decode_from[i] = self.T[i] if g.ragged else g.T
+                if self.pool is not None:                        # reserved up front: nothing is allocated inside a step, nobody is preempted
+                    self.blocks[i] = self.pool.alloc(blocks_for(g.T + self.budget[i]))
+                    if self.blocks[i] is None:
+                        raise ValueError(f"request {i}: the pool ran out of blocks behind the admission gate")
+                    self._rows_reserved += g.T + self.budget[i]
+        if self.pool is not None:
+            self.stats["kv_blocks_peak"] = self.pool.peak
+            self.stats["kv_rows_reserved_peak"] = max(self.stats["kv_rows_reserved_peak"], self._rows_reserved)
         self.stats["admission_groups"] += len(groups)
         return groups
+
+    def _blocks_needed(self, groups: List[Group], g: Optional[Group], i: int) -> int:
+        """blocks the groups of this boundary reserve once request i has joined group g (None: a group of its own)"""
+        need = 0
+        for h in groups:
+            t = max(h.T, self.T[i]) if h is g else h.T
+            need += sum(blocks_for(t + self.budget[j]) for j in h.requests + ([i] if h is g else []))
+        return need + (blocks_for(self.T[i] + self.budget[i]) if g is None else 0)
 
     def _finish(self, b: int, tokens: Sequence[int], extra=None) -> None:
         i = self.slot_req[b]
@@ -244,6 +345,9 @@ class InflightScheduler:
         self.stats["tokens"] += len(tokens)
         self.stats["stop_hits"] += stop_hit(self.results[i], self.stops[i])
         self.slot_req[b] = None
+        if self.pool is not None:                                # harvested (finished, stopped or cancelled): the reservation returns
+            self.pool.free(self.blocks.pop(i))
+            self._rows_reserved -= self.decode_from[i] + self.budget[i]
 
     def cancel(self, b: int, tokens: Sequence[int], extra=None) -> None:
         """The callback cancelled slot b's request at this boundary: it is complete with the tokens delivered so far (extra: their
@@ -296,6 +400,8 @@ class InflightScheduler:
         they were delivered.  Returns them."""
         self.stats["steps"] += n_steps
         self.stats["slot_steps_total"] += n_steps * self.slots
+        if self.pool is not None:
+            self._waited = False
         done = []
         for b, i in enumerate(self.slot_req):
             if i is None:
@@ -324,6 +430,15 @@ class InflightScheduler:
         return [RequestOutput(self.results[i], *self.extras[i]) for i in range(self.n)]
 
 
+def kv_accounting(sched: "InflightScheduler", row_bytes: int) -> Dict[str, int]:
+    """bytes of a finished (or running) paged queue, row_bytes = bytes of ONE K/V row over all layers, K and V, all heads:
+    kv_bytes: the pool; kv_bytes_peak: the blocks reserved at the peak; kv_bytes_contiguous: what slots x ctx_max rows would have taken"""
+    if sched.pool is None:
+        raise ValueError("kv_accounting: the scheduler has no pool (kv_pool_tokens)")
+    return dict(kv_bytes=sched.pool.n_blocks * KV_BLOCK_ROWS * int(row_bytes), kv_bytes_peak=sched.pool.peak * KV_BLOCK_ROWS * int(row_bytes),
+                kv_bytes_contiguous=sched.slots * sched.ctx_max * int(row_bytes))
+
+
 def step_bound(budgets: Sequence[int], slots: int, steps_per_sync: int) -> float:
     """Upper bound on the decode steps of a queue: (sum(n_i) + N (c - 1)) / B + max(n_i) + c.  Until the queue empties every slot is
     busy or inside a gap of at most c - 1 steps behind a finish; afterwards at most the longest request plus one chunk remains."""
@@ -340,18 +455,19 @@ def static_batch_steps(budgets: Sequence[int], slots: int) -> int:
 
 def simulate(budgets: Sequence[int], slots: int, steps_per_sync: int, eos_at: Optional[Dict[int, int]] = None, prompt_lens=None, has_image=None,
              max_position_embeddings: int = 1 << 20, image_at_head: bool = False, share_prefix: bool = False, logprobs: Optional[int] = None,
-             targets=None, stops=None, on_tokens: Optional[Callable] = None, token_of: Optional[Callable[[int, int], int]] = None):
+             targets=None, stops=None, on_tokens: Optional[Callable] = None, token_of: Optional[Callable[[int, int], int]] = None,
+             kv_pool_tokens: Optional[int] = None, watch: Optional[Callable] = None):
     """Drives a scheduler with the host model of the slot step and a stepper that emits token (request, k) = 1000 * request + k, or the
     eos id 0 as request i's eos_at[i]-th token.  Returns (scheduler, log of (boundary, slot, request) admissions).
     logprobs / targets: the scheduler's; a forced request emits its targets instead, and token t of request i scores
     -(i + t / 1000) with top ids [t * 10 + r] and top logprobs [-(i + r)] (a stand-in for the device buffers).
     stops: the scheduler's (per request); the slot table carries them as the device table does.  on_tokens: the streaming callback of
     generate_many, called as the slots loop calls it; a true return value cancels.  token_of(i, k): request i's k-th token (1-based)
-    instead of 1000 * (i + 1) + k."""
+    instead of 1000 * (i + 1) + k.  kv_pool_tokens: the scheduler's; watch(scheduler) is called after every admission."""
     n = len(budgets)
     eos_at = eos_at or {}
     sch = InflightScheduler(prompt_lens or [4] * n, budgets, has_image or [False] * n, slots, max_position_embeddings, image_at_head, steps_per_sync,
-                            share_prefix, logprobs, targets, stops)
+                            share_prefix, logprobs, targets, stops, kv_pool_tokens)
     B = sch.slots
     use_stops = any(x is not None for x in sch.stops)
     slot_stops: List[List[List[int]]] = [[] for _ in range(B)]
@@ -376,6 +492,8 @@ def simulate(budgets: Sequence[int], slots: int, steps_per_sync: int, eos_at: Op
     while not sch.finished:
         while True:                                              # a request that ends at its first token frees its slot at once
             groups = sch.admit(sch.free_slots())
+            if watch is not None:
+                watch(sch)
             if not groups:
                 break
             for g in groups:

@@ -207,7 +207,7 @@ class TextStops:
 
 @torch.inference_mode()
 def chat_many(model, items, generation_config=None, max_batch=64, share_prefix=False, generation_configs=None, seeds=None, prefix_cache=None,
-              logprobs=None, constraints=None, stop=None, stops=None, on_text=None):
+              logprobs=None, constraints=None, stop=None, stops=None, on_text=None, kv_pool_tokens=None):
     """The bulk form of chat(): items = [(image, text) or (image, text, history), ...] -> [(response, history), ...].  Every prompt is built as
     chat() builds it, the queue is answered by model.generate_many (in-flight batching over max_batch slots) and every response is appended
     to its item's history exactly as chat() appends it.  share_prefix: generate_many's switch -- the system prompt every item begins with and the
@@ -227,10 +227,12 @@ def chat_many(model, items, generation_config=None, max_batch=64, share_prefix=F
     was delivered: it can run up to generate_many's steps_per_sync tokens past the string.  Strings are NOT converted into generate_many's
     `stop_sequences`: a sentencepiece tokenisation depends on context, so no token sequence stands for a string.
     on_text=fn: the streamed form, fn(i, text_so_far, finished) once per boundary for every item that produced tokens, text_so_far
-    already cut at a stop string; exactly one call per item has finished=True and it is the last."""
+    already cut at a stop string; exactly one call per item has finished=True and it is the last.
+    kv_pool_tokens=n (generate_many's; None: nothing changes): the slots share a paged K/V pool of ceil(n / 16) blocks of 16 rows."""
     from . import constraints as _constraints
-    from .inflight import check_logprobs
+    from .inflight import check_kv_pool_tokens, check_logprobs
     logprobs = check_logprobs(logprobs)
+    check_kv_pool_tokens(kv_pool_tokens)
     if constraints is not None:
         constraints = _constraints.from_items(constraints, len(items))
     for name, lst in (("generation_configs", generation_configs), ("seeds", seeds)):
@@ -260,6 +262,7 @@ def chat_many(model, items, generation_config=None, max_batch=64, share_prefix=F
     outs = model.generate_many(requests, max_batch=max_batch, generation_config=gc, share_prefix=share_prefix,
                                **({} if prefix_cache is None else dict(prefix_cache=prefix_cache)),
                                **({} if logprobs is None else dict(logprobs=logprobs)),
+                               **({} if kv_pool_tokens is None else dict(kv_pool_tokens=kv_pool_tokens)),
                                **(dict(on_tokens=text_stops.on_tokens) if text_stops.active else {}))
     results = []
     for i, (out, history) in enumerate(zip(outs, histories)):

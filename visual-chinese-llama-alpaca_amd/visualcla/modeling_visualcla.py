@@ -1364,7 +1364,7 @@ class VisualCLAModel:
     @torch.no_grad()
     def generate_many(self, requests, max_batch: int = 64, generation_config=None, steps_per_sync: int = 8, use_graph: Optional[bool] = None,
                       share_prefix: bool = False, prefix_pool_tokens: Optional[int] = None, prefix_cache=None, logprobs: Optional[int] = None,
-                      on_tokens=None, **kwargs):
+                      on_tokens=None, kv_pool_tokens: Optional[int] = None, **kwargs):
         """In-flight batching over a queue: -> List[LongTensor [n_i]] in request order, the NEW tokens of every request, its eos included
         and nothing behind it.  requests: dicts with `input_ids` ([T] or [1, T]), optional `pixel_values`, `attention_mask`, `max_new_tokens`
         (default: the config's budget by generate()'s rules for that prompt), `generation_config`, `seed`.
@@ -1436,10 +1436,24 @@ class VisualCLAModel:
         the last, a chunk holds at most steps_per_sync + 1 tokens.  A call that returns a true value CANCELS its request at this
         boundary: the request is complete with the tokens delivered so far (with logprobs, their arrays) and its slot is refilled
         at once.  An exception raised by fn propagates.  With `stop_sequences` or `on_tokens` a queue of one request (or max_batch=1)
-        takes the slots route at one slot.  last_inflight_stats holds `stop_requests`, `stop_hits`, `cancelled`, `stream_calls`."""
-        from .inflight import InflightScheduler, RequestOutput, check_logprobs, check_stop_sequences
+        takes the slots route at one slot.  last_inflight_stats holds `stop_requests`, `stop_hits`, `cancelled`, `stream_calls`.
+
+        kv_pool_tokens=n (a positive int; None: nothing changes): a PAGED K/V cache (visualcla/inflight.py, csrc/attention_decode.hip,
+        DESIGN.md section 7k).  Instead of `max_batch` x ctx_max rows the slots share one pool of ceil(n / 16) blocks of 16 rows, and
+        a block table in device memory tells the decode attention where every slot's rows live.  A request reserves
+        ceil((T_group + budget) / 16) blocks when it is admitted and returns them when it is harvested; requests are admitted in
+        arrival order, and the head of the queue waits at a boundary while its blocks do not fit.  Same results, bit for bit the
+        same schedule whenever nothing waits.  A queue in which a request alone needs more blocks than the pool holds is refused up
+        front, naming the requests.  Not beside share_prefix / prefix_cache (the ragged admission pass has no paged form).  With it a
+        queue of one request (or max_batch=1) takes the slots route at one slot.  last_inflight_stats gains `kv_pool_blocks`,
+        `kv_blocks_peak`, `kv_bytes` (the pool), `kv_bytes_contiguous` (what max_batch x ctx_max rows would have taken),
+        `kv_rows_reserved_peak`, `admission_waits_blocks` (boundaries at which a free slot stayed empty because the head did not fit)."""
+        from .inflight import InflightScheduler, RequestOutput, check_kv_pool_tokens, check_logprobs, check_stop_sequences
         from .prefix_cache import PrefixCache
         logprobs = check_logprobs(logprobs)                       # before anything else: the argument by name
+        if check_kv_pool_tokens(kv_pool_tokens) is not None and (share_prefix or prefix_cache is not None):
+            raise ValueError(f"generate_many: kv_pool_tokens with {'prefix_cache' if prefix_cache is not None else 'share_prefix=True'} (the ragged admission "
+                             "pass needs a paged vcla_attn_extend_rows, its fp32 route a paged prefill)")
         if on_tokens is not None and not callable(on_tokens):
             raise ValueError(f"generate_many: on_tokens must be a callable fn(i, tokens, finished) or None (got {type(on_tokens).__name__})")
         if prefix_cache is not None:
@@ -1491,8 +1505,8 @@ class VisualCLAModel:
             extra_stats.update(ctable.stats())
         # raises for a prompt that leaves no room, by index, before any kernel runs
         sched = InflightScheduler(lens, budgets, [r["px"] is not None for r in reqs], max_batch, t["max_position_embeddings"], self.image_at_head,
-                                  steps_per_sync, share_prefix=bool(share_prefix), logprobs=logprobs, targets=targets, stops=stops)
-        slots_only = prefix_cache is not None or logprobs is not None or ctable is not None or on_tokens is not None or any(x is not None for x in sched.stops)
+                                  steps_per_sync, share_prefix=bool(share_prefix), logprobs=logprobs, targets=targets, stops=stops, kv_pool_tokens=kv_pool_tokens)
+        slots_only = kv_pool_tokens is not None or prefix_cache is not None or logprobs is not None or ctable is not None or on_tokens is not None or any(x is not None for x in sched.stops)
         if use_graph is None:
             use_graph = os.environ.get("VCLA_DECODE_GRAPH", "1") != "0"
         if sched.slots == 1 and (not slots_only or not reqs):

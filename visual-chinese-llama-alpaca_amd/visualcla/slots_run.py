@@ -10,6 +10,7 @@ from typing import Dict, List, Optional
 import torch
 
 from . import _lib, prefix
+from .inflight import kv_accounting
 
 RAGGED_MAX_ROWS = 8192      # packed rows of one vcla_llama_extend_rows call (its workspace is sized for them); longer passes are cut
 
@@ -48,6 +49,15 @@ class Stops:
 
     def __init__(self, table: torch.Tensor):
         self.table, self.args = table, _lib.stop_args(table)
+
+
+class Pages:
+    """kv_pool_tokens: the slots share a pool [L, 2, H, n_blocks * 16, d] (SlotsRun.kv) behind the per-slot block table int32 [B, ld]
+    (-1: no block; every slot starts without blocks) and the step's vcla_kv_pages over it"""
+    __slots__ = ("table", "args", "n_blocks")
+
+    def __init__(self, table: torch.Tensor, n_blocks: int):
+        self.table, self.n_blocks, self.args = table, n_blocks, _lib.kv_pages(table, n_blocks)
 
 
 class PrefixShare:
@@ -150,8 +160,9 @@ class SlotsRun:
     logprobs (k or None): the step also runs the stats pass and the pick (csrc/logprobs.hip); sched.targets[i] forces request i.
     constraints (a constraints.Table or None): the step also runs the mask and the transition (csrc/constrain.hip).
     sched.stops[i]: request i's stop sequences -- with any, the bookkeeping launch of the step decides them from a per-slot table.
-    on_tokens (a callable or None): every boundary hands each running request's new tokens to it; a true return value cancels the request."""
-    stops = on_tokens = None    # (the defaults of a run assembled by hand, as the host tests do)
+    on_tokens (a callable or None): every boundary hands each running request's new tokens to it; a true return value cancels the request.
+    sched.pool (kv_pool_tokens): the cache is a pool of 16-row blocks behind a per-slot block table; sched.blocks[i] are request i's."""
+    stops = on_tokens = pages = None    # (the defaults of a run assembled by hand, as the host tests do)
 
     def __init__(self, model, gc, reqs, sched, use_graph, plan=None, gcs=None, seeds=None, pstate=None, logprobs=None, constraints=None, on_tokens=None):
         self.m, self.reqs, self.sched, self.use_graph, self.dev = model, reqs, sched, use_graph, model._device
@@ -179,7 +190,13 @@ class SlotsRun:
         self.cur = cur = model._typed_buf("if_cur", (B,), torch.int64).zero_()
         self.uni = uni = model._typed_buf("if_uni", (cap, B), torch.float32) if any(draws) and samp_kw is not None else None
         H, d = t["num_attention_heads"], t["hidden_size"] // t["num_attention_heads"]
-        self.kv = model._typed_buf("if_kv", (t["num_hidden_layers"], 2, B, H, ctx_max, d), model._dtype)
+        self.pages = None
+        if sched.pool is not None:                              # one sequence of n_blocks * 16 rows: a (layer, K or V, head) slab stays one buffer
+            nb = sched.pool.n_blocks
+            self.kv = model._typed_buf("if_kv_pool", (t["num_hidden_layers"], 2, H, nb * _lib.KV_BLOCK_ROWS, d), model._dtype)
+            self.pages = Pages(model._typed_buf("if_kv_table", (B, (ctx_max + _lib.KV_BLOCK_ROWS - 1) // _lib.KV_BLOCK_ROWS), torch.int32).fill_(-1), nb)
+        else:
+            self.kv = model._typed_buf("if_kv", (t["num_hidden_layers"], 2, B, H, ctx_max, d), model._dtype)
         self.km = model._typed_buf("if_km", (B, ctx_max), torch.int32).fill_(1)
         self.lp = None
         ws_bytes = lib.vcla_llama_workspace_bytes(model._ctx, B, 1)
@@ -233,6 +250,9 @@ class SlotsRun:
             t_steps += time.perf_counter() - t1
         # beside the counters: host seconds spent in admission / in steps, and the position every request's slot decoded from (its group's longest prompt)
         self.m.last_inflight_stats = stats = dict(sched.stats, admission_s=t_adm, steps_s=t_steps, ctx_max=sched.ctx_max, decode_from=[sched.decode_from[i] for i in range(sched.n)])
+        if self.pages is not None:                              # kv_bytes: the pool; kv_bytes_contiguous: what B x ctx_max rows would have taken
+            row_bytes = self.kv[:, :, :, 0].numel() * self.kv.element_size()
+            stats.update(kv_accounting(sched, row_bytes))
         if share is not None:
             stats.update(rows_reused=share.reused, rows_computed=share.computed, vision_runs=share.vision, pool_entries=len(share.plan.entries),
                          pool_bytes=share.pool.numel() * share.pool.element_size(), pool_rows=int(share.pool.shape[0]),
@@ -375,11 +395,26 @@ class SlotsRun:
         if m._inflight_logits_tap is not None:
             m._inflight_logits_tap.append((list(g.requests), logits.detach().clone()))
         sl = torch.tensor(g.slots, device=dev)
-        self.kv[:, :, sl, :, :Tg, :] = own.kv
+        if self.pages is not None:
+            self.fill_pages(g, own.kv, Tg)
+        else:
+            self.kv[:, :, sl, :, :Tg, :] = own.kv
         self.km[sl] = 1
         if am2 is not None:
             self.km[sl, :Tg] = am2.to(torch.int32)
         self.start_slots(g.requests, g.slots, self.first_token(logits, g.requests, sl).tolist(), Tg)      # (.tolist() synchronises)
+
+    def fill_pages(self, g, own_kv: torch.Tensor, Tg: int) -> None:
+        """paged admission: the table rows of the slots the group fills, validated on the host before the upload (entries in range, no
+        block owned twice -- the live slots' blocks included --, enough blocks for T_group + budget), then ONE indexed copy of the
+        private cache's rows [0, T_group) into the slots' blocks"""
+        sched, pg, R = self.sched, self.pages, _lib.KV_BLOCK_ROWS
+        owned = [b for i, blocks in sched.blocks.items() if i not in g.requests for b in blocks]
+        rows = _lib.kv_page_rows([sched.blocks[i] for i in g.requests], [Tg + sched.budget[i] for i in g.requests], pg.n_blocks, pg.table.shape[1], owned)
+        pg.table[torch.tensor(g.slots, device=self.dev)] = rows.to(self.dev)
+        idx = torch.tensor([sched.blocks[i][r // R] * R + r % R for i in g.requests for r in range(Tg)], device=self.dev)
+        L, _, G, H, _, d = own_kv.shape
+        self.kv[:, :, :, idx, :] = own_kv.permute(0, 1, 3, 2, 4, 5).reshape(L, 2, H, G * Tg, d)
 
     def admit_ragged(self, g) -> None:
         """share_prefix=True: the requests admitted at one boundary, every one at position 0 of its slot.  In the passes of prefix.passes: copy
@@ -452,12 +487,14 @@ class SlotsRun:
     def decode_chunk(self, n: int) -> None:
         """n steps of every live slot, one call; the per-slot tables, the logprob block, the constraints and the stop table are null where the feature is off"""
         per, ws = self.per, self.ws
-        _lib.check(self.lib.vcla_llama_decode_slots_stops(
-            self.m._ctx, C.byref(self.slot_args), n, self.kv.data_ptr(), self.sched.ctx_max, self.km.data_ptr(), ws.data_ptr(), ws.numel(),
-            int(self.use_graph), C.byref(self.samp) if self.samp is not None else None, per.eos_dev.data_ptr() if per is not None else None,
-            _lib.ptr(per.rows_dev) if per is not None else None, C.byref(self.lp.args) if self.lp is not None else None,
-            C.byref(self.cons.args) if self.cons is not None else None, C.byref(self.stops.args) if self.stops is not None else None,
-            _lib.stream_ptr()))
+        args = (self.m._ctx, C.byref(self.slot_args), n, self.kv.data_ptr(), self.sched.ctx_max, self.km.data_ptr(), ws.data_ptr(), ws.numel(),
+                int(self.use_graph), C.byref(self.samp) if self.samp is not None else None, per.eos_dev.data_ptr() if per is not None else None,
+                _lib.ptr(per.rows_dev) if per is not None else None, C.byref(self.lp.args) if self.lp is not None else None,
+                C.byref(self.cons.args) if self.cons is not None else None, C.byref(self.stops.args) if self.stops is not None else None)
+        if self.pages is not None:                              # the pool behind the block table: ctx_max is then the logical cap of a slot
+            _lib.check(self.lib.vcla_llama_decode_slots_paged(*args, C.byref(self.pages.args), _lib.stream_ptr()))
+        else:
+            _lib.check(self.lib.vcla_llama_decode_slots_stops(*args, _lib.stream_ptr()))
 
     def harvest(self, host) -> None:
         """`host`: the slot table after a chunk.  The finished slots' columns of the history and of the logprob buffers go to the scheduler.
