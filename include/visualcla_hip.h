@@ -858,6 +858,31 @@ int vcla_llama_decode_slots_paged(vcla_ctx* ctx, const vcla_slot_args* slots, in
                                   const int32_t* eos_rows, const vcla_sample_row* rows, const vcla_logprob_args* logprobs,
                                   const vcla_constrain_args* constraints, const vcla_stop_args* stops, const vcla_kv_pages* pages, void* stream);
 
+/* ---------------------------------------------------------------- ragged admission over the pool (prompt blocks shared by reference)
+   The ragged admission pass (vcla_attn_extend_rows, vcla_llama_extend_rows above) on the paged cache: with a block table two slots can
+   NAME the same pool block, so the leading full 16-row blocks of a prompt that several requests share are stored once and read by all
+   of them -- no copy.  The kernels only read a block below a block's `pos`; the host guarantees that every holder of a block with
+   several holders has pos at or behind its end (a block with more than one holder is never written).
+   Additive entries; the ABI version stays 5.
+
+   vcla_attn_extend_rows_paged: vcla_attn_extend_rows with k_pool / v_pool [H][n_blocks * 16][d] (the layer's slabs of the pool), ctx_max
+   the LOGICAL cap of a slot, `pages` the table (pages->ld * 16 >= ctx_max; the slot of a block selects its table row).  Cached keys
+   [0, pos) and the appended rows [pos, pos + rows) go through the table; tile order, split rule, work list, merge, RoPE rounding and
+   arithmetic are those of vcla_attn_extend_rows: out and the appended rows equal that entry on a contiguous cache holding the same rows,
+   bit for bit.  Checks: the table checks of vcla_attn_extend_rows, the `pages` fields as vcla_attn_decode_paged checks them, a head's
+   slab below 4 GiB.  An entry outside [0, n_blocks) is never turned into an address: its cached keys are masked, an append through it is
+   skipped.  Scratch: vcla_attn_extend_rows_scratch_bytes / _bound. */
+int vcla_attn_extend_rows_paged(const void* qkv, void* k_pool, void* v_pool, const float* cos_tab, const float* sin_tab, void* out,
+                                const vcla_extend_seq* seqs, int n_seqs, int M, int B_slots, int H, int d, int ctx_max, float scale, int dtype,
+                                int out_frag, int lists_ready, void* scratch, size_t scratch_bytes, const vcla_kv_pages* pages, void* stream);
+
+/* vcla_llama_extend_rows over the pool: pages NULL is that function.  Otherwise kv_cache is the pool [L][2][H][n_blocks * 16][d], ctx_max
+   the logical cap of a slot, B_slots the rows of the table, and the attention launch of every layer is vcla_attn_extend_rows_paged.  The
+   kernel route only (bf16, head dim 64 / 128, every block <= VCLA_EXTEND_MAX_ROWS rows): anything else returns an error naming the
+   condition and launches nothing.  Workspace: vcla_llama_extend_rows_workspace_bytes. */
+int vcla_llama_extend_rows_paged(vcla_ctx* ctx, const void* inputs_embeds, const vcla_extend_seq* seqs, int n_seqs, void* kv_cache, int B_slots,
+                                 int ctx_max, float* logits, void* ws, size_t ws_bytes, const vcla_kv_pages* pages, void* stream);
+
 /* ---------------------------------------------------------------- debug */
 /* The label of the calling thread's most recent kernel launch through this library ("" before the first): a string literal that
    names the kernel and, for the attention dispatchers (vcla_attention, vcla_attn_decode_*, vcla_attn_verify, the persistent decode

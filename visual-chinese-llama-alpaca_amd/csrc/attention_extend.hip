@@ -23,6 +23,10 @@
 // Second entry, vcla_attn_extend_rows (at the end of the file): the same tile code (ax_block) for the blocks of SEVERAL sequences of a slots
 // cache in one launch -- the ragged admission pass of generate_many(share_prefix=True).  Only the mapping from workgroups to work differs:
 // a 1-D work list of (sequence, q-tile, key split) built on the host, the splits chosen from the total work (rule stated there).
+//
+// PAGED (vcla_attn_extend_rows_paged): the cache is the pool [H][n_blocks * 16][d] of attention_decode.hip's paged form and logical row j of
+// slot b lives at physical row table[b * ld + (j >> 4)] * 16 + (j & 15) of the head's slab.  Only two address computations change -- the
+// cached-row loads of load_tile and the append -- so a paged call is bit for bit the contiguous one over the same rows.
 #include "vcla_common.h"
 #include <vector>
 
@@ -69,6 +73,12 @@ __device__ __forceinline__ int64_t ax_frag_index(int m, int k, int MT) {
     return ((((int64_t)(k >> 5) * MT + (m >> 4)) * 64 + ((k & 31) >> 3) * 16 + (m & 15)) << 3) + (k & 7);
 }
 
+// PAGED: the block table of the launch by value; the contiguous instantiations take an empty struct in its place
+template <bool PAGED> struct AxPages {};
+template <> struct AxPages<true> { const int32_t* table; int ld; int n_blocks; };
+// The table is never written by a kernel that reads it: through the constant address space a load at a wave-uniform index is a scalar load
+typedef const __attribute__((address_space(4))) int32_t* ax_table_p;
+
 struct ExtendPlan { int nw, qb, nqt, S; };
 inline ExtendPlan extend_plan(int R, int H, int p) {
     ExtendPlan e;
@@ -89,11 +99,15 @@ inline ExtendPlan extend_plan(int R, int H, int p) {
 // the block's first row in `out` (0 for a single sequence, its first packed row in vcla_attn_extend_rows); pw0: the [QB][D + 4] fp32 partials
 // of this work item (S > 1); append: this work item writes the head's R new K / V rows.  Shared by both kernels below, which differ only in
 // how a workgroup finds these values.
-template <int D, int NW>
+// PAGED: kb / vb are the head's slab of the pool, trow the slot's row of the block table, n_blocks the pool's size.  A table word outside
+// [0, n_blocks) is never turned into an address: the cached keys of such a block are staged as zeros and masked, an append through it is
+// skipped.  Words are read only for blocks [0, (p - 1) >> 4] (cached keys) and [p >> 4, (p + R - 1) >> 4] (the append): the blocks the
+// sequence owns, because a key clamped to Tk - 1 >= p comes from qkv, never through the table.
+template <int D, int NW, bool PAGED = false>
 __device__ __forceinline__ void ax_block(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ kb, bf16_t* __restrict__ vb,
                                          const float* __restrict__ cos_tab, const float* __restrict__ sin_tab, bf16_t* __restrict__ out, int out_row0,
                                          float* __restrict__ pw0, int R, int H, int p, float scale, int out_mt, int split, int S, int qt_idx, int h,
-                                         bool append) {
+                                         bool append, const int32_t* __restrict__ trow = nullptr, int n_blocks = 0) {
     constexpr int QB = NW * 32, NT = NW * 64;
     constexpr int HALF = D / 2;
     constexpr int KST = D / 32;         // MFMA k-steps over the head dim (Q K^T)
@@ -116,16 +130,34 @@ __device__ __forceinline__ void ax_block(const bf16_t* __restrict__ qkv, bf16_t*
     if (append) {
         for (int idx = tid; idx < R * (CH / 2); idx += NT) {
             const int r = idx / (CH / 2), i = (idx % (CH / 2)) * 8;
+            [[maybe_unused]] int64_t arow = 0;
+            if constexpr (PAGED) {
+                const int word = trow[(p + r) >> 4];
+                if ((unsigned)word >= (unsigned)n_blocks) continue;      // no block behind this row: nothing is written
+                arow = (int64_t)word * VCLA_KV_BLOCK_ROWS + ((p + r) & (VCLA_KV_BLOCK_ROWS - 1));
+            }
             const bf16_t* krow = qh + (int64_t)r * 3 * HD + HD;
             uint4 lo, hi;
             rope_pair(*reinterpret_cast<const uint4*>(krow + i), *reinterpret_cast<const uint4*>(krow + i + HALF),
                       cos_tab + (int64_t)(p + r) * HALF + i, sin_tab + (int64_t)(p + r) * HALF + i, lo, hi);
-            *reinterpret_cast<uint4*>(kb + (int64_t)(p + r) * D + i) = lo;
-            *reinterpret_cast<uint4*>(kb + (int64_t)(p + r) * D + i + HALF) = hi;
+            if constexpr (PAGED) {
+                *reinterpret_cast<uint4*>(kb + arow * D + i) = lo;
+                *reinterpret_cast<uint4*>(kb + arow * D + i + HALF) = hi;
+            } else {
+                *reinterpret_cast<uint4*>(kb + (int64_t)(p + r) * D + i) = lo;
+                *reinterpret_cast<uint4*>(kb + (int64_t)(p + r) * D + i + HALF) = hi;
+            }
         }
         for (int idx = tid; idx < R * CH; idx += NT) {
             const int r = idx / CH, i = (idx % CH) * 8;
-            *reinterpret_cast<uint4*>(vb + (int64_t)(p + r) * D + i) = *reinterpret_cast<const uint4*>(qh + (int64_t)r * 3 * HD + 2 * HD + i);
+            if constexpr (PAGED) {
+                const int word = trow[(p + r) >> 4];
+                if ((unsigned)word >= (unsigned)n_blocks) continue;
+                const int64_t arow = (int64_t)word * VCLA_KV_BLOCK_ROWS + ((p + r) & (VCLA_KV_BLOCK_ROWS - 1));
+                *reinterpret_cast<uint4*>(vb + arow * D + i) = *reinterpret_cast<const uint4*>(qh + (int64_t)r * 3 * HD + 2 * HD + i);
+            } else {
+                *reinterpret_cast<uint4*>(vb + (int64_t)(p + r) * D + i) = *reinterpret_cast<const uint4*>(qh + (int64_t)r * 3 * HD + 2 * HD + i);
+            }
         }
     }
 
@@ -165,15 +197,56 @@ __device__ __forceinline__ void ax_block(const bf16_t* __restrict__ qkv, bf16_t*
 
     // ---- staging: cached rows from the cache, new rows (keys >= p) from qkv with K rotated on the way
     u32x4_t rk[NLD], rv[NLD];
+    // PAGED: the four table words of a 64-key tile (key group t of the tile is logical block tile * 4 + t) as scalar loads: the staging
+    // lanes of one wave and load cover 64 / CH keys aligned to that count, inside ONE 16-row block, so the word a lane needs is
+    // wave-uniform.  The words are fetched at the TOP of the loop trip whose load_tile forms addresses from them (fetch_words), in front
+    // of the barriers around store_tile: the barrier's wait covers them, so no scalar load is outstanding while tile_body reads LDS (a
+    // scalar load in flight would turn its counted LDS waits into waits for everything).  Blocks behind the last cached key are
+    // clamped to it (their keys are >= p and never go through the table).  ok_next / ok_cur: bit t = word t of the tile in flight / in
+    // LDS names a pool block.
+    constexpr int GID = CH * VCLA_KV_BLOCK_ROWS;                     // staging ids per 16-row block
+    static_assert(!PAGED || (XKV == 4 * VCLA_KV_BLOCK_ROWS && (NT <= GID ? GID % NT == 0 : NT % GID == 0)), "a wave's keys of one load sit in one block");
+    [[maybe_unused]] int ok_next = 0, ok_cur = 0;
+    [[maybe_unused]] const int q_wave = NT > GID ? __builtin_amdgcn_readfirstlane(tid / GID) : 0;
+    [[maybe_unused]] int tw[4] = {0, 0, 0, 0};                       // the words of the tile the NEXT load_tile call stages
+    auto fetch_words = [&](int tile) {
+        if constexpr (PAGED) {
+            const ax_table_p ct = (ax_table_p)(uintptr_t)trow;
+            const int lastb = p > 0 ? (p - 1) >> 4 : 0;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const int b = tile * 4 + t;
+                tw[t] = ct[b < lastb ? b : lastb];
+            }
+        }
+    };
     auto load_tile = [&](int tile) {
+        if constexpr (PAGED) {
+            ok_next = 0;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) ok_next |= (int)((unsigned)tw[t] < (unsigned)n_blocks) << t;
+        }
 #pragma unroll
         for (int i = 0; i < NLD; ++i) {
             const int id = i * NT + tid, key = id / CH, ch = id % CH;
             int kg = tile * XKV + key;
             if (kg >= Tk) kg = Tk - 1;           // clamp; masked below
             if (kg < p) {
-                rk[i] = *reinterpret_cast<const u32x4_t*>(kb + (int64_t)kg * D + ch * 8);
-                rv[i] = *reinterpret_cast<const u32x4_t*>(vb + (int64_t)kg * D + ch * 8);
+                if constexpr (PAGED) {
+                    const int q = (i * NT) / GID + q_wave;           // = key >> 4, wave-uniform
+                    const int word = q == 0 ? tw[0] : q == 1 ? tw[1] : q == 2 ? tw[2] : tw[3];
+                    if ((unsigned)word < (unsigned)n_blocks) {
+                        const int64_t row = (int64_t)word * VCLA_KV_BLOCK_ROWS + (kg & (VCLA_KV_BLOCK_ROWS - 1));
+                        rk[i] = *reinterpret_cast<const u32x4_t*>(kb + row * D + ch * 8);
+                        rv[i] = *reinterpret_cast<const u32x4_t*>(vb + row * D + ch * 8);
+                    } else {                                        // no block: zeros (finite under the mask of tile_body), no load
+                        rk[i] = u32x4_t{0u, 0u, 0u, 0u};
+                        rv[i] = u32x4_t{0u, 0u, 0u, 0u};
+                    }
+                } else {
+                    rk[i] = *reinterpret_cast<const u32x4_t*>(kb + (int64_t)kg * D + ch * 8);
+                    rv[i] = *reinterpret_cast<const u32x4_t*>(vb + (int64_t)kg * D + ch * 8);
+                }
             } else {
                 const bf16_t* row = qh + (int64_t)(kg - p) * 3 * HD;
                 const int cl = (ch % (CH / 2)) * 8;
@@ -186,6 +259,7 @@ __device__ __forceinline__ void ax_block(const bf16_t* __restrict__ qkv, bf16_t*
         }
     };
     auto store_tile = [&]() {
+        if constexpr (PAGED) ok_cur = ok_next;
 #pragma unroll
         for (int i = 0; i < NLD; ++i) {
             const int id = i * NT + tid, key = id / CH, ch = id % CH;
@@ -211,6 +285,17 @@ __device__ __forceinline__ void ax_block(const bf16_t* __restrict__ qkv, bf16_t*
                 const bf16x8_t kf = *reinterpret_cast<const bf16x8_t*>(ks + ax_k_off<D>(t * 16 + ql, s * 4 + g));
                 sacc[0][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[0][s], sacc[0][t], 0, 0, 0);
                 sacc[1][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[1][s], sacc[1][t], 0, 0, 0);
+            }
+        }
+        if constexpr (PAGED) {
+            if (ok_cur != 15) {                  // a cached key group without a block (never under a validated table): its keys are masked
+#pragma unroll
+                for (int qt = 0; qt < 2; ++qt)
+#pragma unroll
+                    for (int t = 0; t < NTK; ++t)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+                            if (!((ok_cur >> t) & 1) && kv0 + t * 16 + g * 4 + r < p) sacc[qt][t][r] = -INFINITY;
             }
         }
         // lane holds keys kv0 + t*16 + g*4 + r of query rows qw + qt*16 + ql; row j sees keys <= p + j (wave-uniform test first)
@@ -282,8 +367,12 @@ __device__ __forceinline__ void ax_block(const bf16_t* __restrict__ qkv, bf16_t*
         }
     };
 
-    if (t_lo < t_hi) load_tile(t_lo);
+    if (t_lo < t_hi) {
+        if constexpr (PAGED) fetch_words(t_lo);
+        load_tile(t_lo);
+    }
     for (int tile = t_lo; tile < t_hi; ++tile) {
+        if constexpr (PAGED) fetch_words(tile + 1 < t_hi ? tile + 1 : tile);      // the tile this trip's load_tile stages
         __syncthreads();          // previous tile fully consumed
         store_tile();
         __syncthreads();
@@ -468,17 +557,25 @@ inline size_t rows_lists_bytes(size_t n_work, size_t n_merge) { return ax_up256(
 thread_local RowsPlan g_rows_plan;       // (thread_local: the lists outlive the call that copies them to the device)
 }  // namespace
 
-template <int D, int NW>
+template <int D, int NW, bool PAGED = false>
 __global__ __launch_bounds__(NW * 64) void attn_extend_rows_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ kc, bf16_t* __restrict__ vc,
                                                                    const float* __restrict__ cos_tab, const float* __restrict__ sin_tab,
                                                                    bf16_t* __restrict__ out, float* __restrict__ part, const AxWork* __restrict__ work,
-                                                                   int H, int ctx_max, float scale, int out_mt) {
+                                                                   int H, int ctx_max, float scale, int out_mt, AxPages<PAGED> pg) {
     constexpr int QB = NW * 32;
     const AxWork w = work[blockIdx.x];           // workgroup-uniform: scalar loads, no vector register held for it
     const int h = blockIdx.y;
-    const int64_t head = ((int64_t)w.slot * H + h) * ctx_max * D;
-    ax_block<D, NW>(qkv + (int64_t)w.m0 * 3 * H * D, kc + head, vc + head, cos_tab, sin_tab, out, w.m0,
-                    part + ((int64_t)w.part * H + h) * QB * (D + 4), w.R, H, w.p, scale, out_mt, w.split, w.S, w.qt, h, w.split == 0 && w.qt == 0);
+    if constexpr (PAGED) {
+        // the pool is ONE sequence of n_blocks * 16 rows per head; the slot enters through its row of the table
+        const int64_t head = (int64_t)h * pg.n_blocks * VCLA_KV_BLOCK_ROWS * D;
+        ax_block<D, NW, true>(qkv + (int64_t)w.m0 * 3 * H * D, kc + head, vc + head, cos_tab, sin_tab, out, w.m0,
+                              part + ((int64_t)w.part * H + h) * QB * (D + 4), w.R, H, w.p, scale, out_mt, w.split, w.S, w.qt, h,
+                              w.split == 0 && w.qt == 0, pg.table + (int64_t)w.slot * pg.ld, pg.n_blocks);
+    } else {
+        const int64_t head = ((int64_t)w.slot * H + h) * ctx_max * D;
+        ax_block<D, NW>(qkv + (int64_t)w.m0 * 3 * H * D, kc + head, vc + head, cos_tab, sin_tab, out, w.m0,
+                        part + ((int64_t)w.part * H + h) * QB * (D + 4), w.R, H, w.p, scale, out_mt, w.split, w.S, w.qt, h, w.split == 0 && w.qt == 0);
+    }
 }
 
 // the merge of attn_extend_merge_kernel per list entry: partials [part][H][QB][D + 4]
@@ -528,10 +625,19 @@ extern "C" size_t vcla_attn_extend_rows_scratch_bound(int M, int n_seqs, int H, 
 
 template <int D, int NW>
 static int launch_extend_rows(const void* qkv, void* kc, void* vc, const float* cos_tab, const float* sin_tab, void* out, int H, int ctx_max, float scale,
-                              int out_mt, const RowsPlan& pl, const AxWork* work, const AxMerge* merge, float* part, hipStream_t s) {
-    attn_extend_rows_kernel<D, NW><<<dim3((unsigned)pl.work.size(), H), NW * 64, 0, s>>>((const bf16_t*)qkv, (bf16_t*)kc, (bf16_t*)vc, cos_tab, sin_tab,
-                                                                                        (bf16_t*)out, part, work, H, ctx_max, scale, out_mt);
-    VCLA_CHECK_LAUNCH("attn_extend_rows_kernel");
+                              int out_mt, const RowsPlan& pl, const AxWork* work, const AxMerge* merge, float* part, hipStream_t s,
+                              const vcla_kv_pages* pages = nullptr) {
+    if (pages) {
+        attn_extend_rows_kernel<D, NW, true><<<dim3((unsigned)pl.work.size(), H), NW * 64, 0, s>>>(
+            (const bf16_t*)qkv, (bf16_t*)kc, (bf16_t*)vc, cos_tab, sin_tab, (bf16_t*)out, part, work, H, ctx_max, scale, out_mt,
+            AxPages<true>{pages->table, pages->ld, pages->n_blocks});
+        VCLA_CHECK_LAUNCH(D == 128 ? (NW == 2 ? "attn_extend_rows_kernel<D=128,NW=2,PAGED=true>" : "attn_extend_rows_kernel<D=128,NW=4,PAGED=true>")
+                                   : (NW == 2 ? "attn_extend_rows_kernel<D=64,NW=2,PAGED=true>" : "attn_extend_rows_kernel<D=64,NW=4,PAGED=true>"));
+    } else {
+        attn_extend_rows_kernel<D, NW><<<dim3((unsigned)pl.work.size(), H), NW * 64, 0, s>>>((const bf16_t*)qkv, (bf16_t*)kc, (bf16_t*)vc, cos_tab, sin_tab,
+                                                                                            (bf16_t*)out, part, work, H, ctx_max, scale, out_mt, AxPages<false>{});
+        VCLA_CHECK_LAUNCH("attn_extend_rows_kernel");
+    }
     if (!pl.merge.empty()) {
         constexpr int RPB = 256 / (D / 4);
         attn_extend_rows_merge_kernel<D><<<dim3((unsigned)pl.merge.size() * (NW * 32 / RPB), H), 256, 0, s>>>(part, (bf16_t*)out, merge, H, NW * 32, out_mt);
@@ -540,9 +646,10 @@ static int launch_extend_rows(const void* qkv, void* kc, void* vc, const float* 
     return VCLA_OK;
 }
 
-extern "C" int vcla_attn_extend_rows(const void* qkv, void* k_cache, void* v_cache, const float* cos_tab, const float* sin_tab, void* out,
-                                     const vcla_extend_seq* seqs, int n_seqs, int M, int B_slots, int H, int d, int ctx_max, float scale, int dtype,
-                                     int out_frag, int lists_ready, void* scratch, size_t scratch_bytes, void* stream) {
+// pages: the paged entry (checked there); NULL: the contiguous slots cache
+static int attn_extend_rows_impl(const void* qkv, void* k_cache, void* v_cache, const float* cos_tab, const float* sin_tab, void* out,
+                                 const vcla_extend_seq* seqs, int n_seqs, int M, int B_slots, int H, int d, int ctx_max, float scale, int dtype,
+                                 int out_frag, int lists_ready, void* scratch, size_t scratch_bytes, void* stream, const vcla_kv_pages* pages) {
     VCLA_REQUIRE(dtype == VCLA_BF16, VCLA_ERR_BAD_DTYPE, "attn_extend_rows: bad dtype %d (bf16 rows and a bf16 cache only)", dtype);
     VCLA_REQUIRE(d == 64 || d == 128, VCLA_ERR_BAD_SHAPE, "attn_extend_rows: head dim %d not in {64,128}", d);
     VCLA_REQUIRE(seqs && n_seqs >= 1 && M >= 1 && B_slots >= 1 && n_seqs <= B_slots && H > 0 && ctx_max > 0, VCLA_ERR_BAD_SHAPE,
@@ -586,7 +693,7 @@ extern "C" int vcla_attn_extend_rows(const void* qkv, void* k_cache, void* v_cac
     }
     const int out_mt = out_frag ? (M + 15) / 16 : 0;
     void *kc = k_cache, *vc = v_cache;
-#define XR_CASE(DD, NN) return launch_extend_rows<DD, NN>(qkv, kc, vc, cos_tab, sin_tab, out, H, ctx_max, scale, out_mt, pl, work, merge, part, s)
+#define XR_CASE(DD, NN) return launch_extend_rows<DD, NN>(qkv, kc, vc, cos_tab, sin_tab, out, H, ctx_max, scale, out_mt, pl, work, merge, part, s, pages)
     if (d == 64) {
         if (pl.nw == 2) XR_CASE(64, 2);
         XR_CASE(64, 4);
@@ -594,4 +701,28 @@ extern "C" int vcla_attn_extend_rows(const void* qkv, void* k_cache, void* v_cac
     if (pl.nw == 2) XR_CASE(128, 2);
     XR_CASE(128, 4);
 #undef XR_CASE
+}
+
+extern "C" int vcla_attn_extend_rows(const void* qkv, void* k_cache, void* v_cache, const float* cos_tab, const float* sin_tab, void* out,
+                                     const vcla_extend_seq* seqs, int n_seqs, int M, int B_slots, int H, int d, int ctx_max, float scale, int dtype,
+                                     int out_frag, int lists_ready, void* scratch, size_t scratch_bytes, void* stream) {
+    return attn_extend_rows_impl(qkv, k_cache, v_cache, cos_tab, sin_tab, out, seqs, n_seqs, M, B_slots, H, d, ctx_max, scale, dtype, out_frag, lists_ready,
+                                 scratch, scratch_bytes, stream, nullptr);
+}
+
+// The same launch over a pool of 16-row blocks [H][n_blocks * 16][d] behind the block table `pages` (device memory, [B_slots][ld], -1 = none):
+// ctx_max is the logical cap of a slot, only addresses take the pool.  The caller validates the table (a block with several holders is
+// only ever read: every holder's pos lies at or behind its end); the kernel never forms an address from an entry outside [0, n_blocks).
+extern "C" int vcla_attn_extend_rows_paged(const void* qkv, void* k_pool, void* v_pool, const float* cos_tab, const float* sin_tab, void* out,
+                                           const vcla_extend_seq* seqs, int n_seqs, int M, int B_slots, int H, int d, int ctx_max, float scale, int dtype,
+                                           int out_frag, int lists_ready, void* scratch, size_t scratch_bytes, const vcla_kv_pages* pages, void* stream) {
+    VCLA_REQUIRE(pages && pages->table && pages->n_blocks >= 1, VCLA_ERR_BAD_ARG, "attn_extend_rows_paged: a null block table, or an empty pool");
+    VCLA_REQUIRE(d == 64 || d == 128, VCLA_ERR_BAD_SHAPE, "attn_extend_rows_paged: head dim %d not in {64,128}", d);
+    VCLA_REQUIRE(ctx_max > 0 && (int64_t)pages->ld * VCLA_KV_BLOCK_ROWS >= ctx_max, VCLA_ERR_BAD_SHAPE,
+                 "attn_extend_rows_paged: a table row of %d blocks does not cover ctx_max %d", pages->ld, ctx_max);
+    // (row * d elements of 2 bytes stay a 32-bit offset inside a head's slab, as in vcla_attn_decode_paged)
+    VCLA_REQUIRE((int64_t)pages->n_blocks * VCLA_KV_BLOCK_ROWS * d * 2 < ((int64_t)1 << 32), VCLA_ERR_BAD_SHAPE,
+                 "attn_extend_rows_paged: n_blocks=%d: a head's slab must stay below 4 GiB", pages->n_blocks);
+    return attn_extend_rows_impl(qkv, k_pool, v_pool, cos_tab, sin_tab, out, seqs, n_seqs, M, B_slots, H, d, ctx_max, scale, dtype, out_frag, lists_ready,
+                                 scratch, scratch_bytes, stream, pages);
 }

@@ -874,8 +874,13 @@ static int llama_layer(vcla_ctx* ctx, hipStream_t s, const LlamaLayer& L, const 
             // ragged admission: the T packed rows are the blocks of several slots, each at its own position
             RUN(gemm_ds(ctx, s, w.h, L.wqkv, L.vqkv, nullptr, 0, w.qkv, 3 * D, nullptr, M, 3 * D, D, VCLA_EPI_NONE, 0,
                         a_def ? w.ssq : nullptr, a_def ? ctx->run.ssq_parts : 0));
-            RUN(vcla_attn_extend_rows(w.qkv, kc, vc, ctx->rope_cos, ctx->rope_sin, w.ao, ctx->run.rows_seqs, ctx->run.rows_n, T, ctx->run.cache_seqs, H, d,
-                                      ctx_max, scale_, dt, /*out_frag=*/1, ctx->run.rows_lists_ready, ctx->run.extend_scratch, ctx->run.extend_scratch_bytes, s));
+            if (pages)       // the pool behind the block table (vcla_llama_extend_rows_paged): the same launch through the table
+                RUN(vcla_attn_extend_rows_paged(w.qkv, kc, vc, ctx->rope_cos, ctx->rope_sin, w.ao, ctx->run.rows_seqs, ctx->run.rows_n, T, ctx->run.cache_seqs,
+                                                H, d, ctx_max, scale_, dt, /*out_frag=*/1, ctx->run.rows_lists_ready, ctx->run.extend_scratch,
+                                                ctx->run.extend_scratch_bytes, pages, s));
+            else
+                RUN(vcla_attn_extend_rows(w.qkv, kc, vc, ctx->rope_cos, ctx->rope_sin, w.ao, ctx->run.rows_seqs, ctx->run.rows_n, T, ctx->run.cache_seqs, H, d,
+                                          ctx_max, scale_, dt, /*out_frag=*/1, ctx->run.rows_lists_ready, ctx->run.extend_scratch, ctx->run.extend_scratch_bytes, s));
             ctx->run.rows_lists_ready = true;
         } else if (ctx->run.extend) {
             // a session's new block: the T rows of one sequence at pos0 .. over its cached rows [0, pos0)
@@ -932,8 +937,12 @@ static int llama_layer(vcla_ctx* ctx, hipStream_t s, const LlamaLayer& L, const 
                              ctx->run.verify_scratch, ctx->run.verify_scratch_bytes, s));
     } else if (ctx->run.rows_seqs) {
         // ragged admission: the blocks of several slots in one launch
-        RUN(vcla_attn_extend_rows(w.qkv, kc, vc, ctx->rope_cos, ctx->rope_sin, w.ao, ctx->run.rows_seqs, ctx->run.rows_n, T, ctx->run.cache_seqs, H, d,
-                                  ctx_max, scale, dt, 0, ctx->run.rows_lists_ready, ctx->run.extend_scratch, ctx->run.extend_scratch_bytes, s));
+        if (pages)
+            RUN(vcla_attn_extend_rows_paged(w.qkv, kc, vc, ctx->rope_cos, ctx->rope_sin, w.ao, ctx->run.rows_seqs, ctx->run.rows_n, T, ctx->run.cache_seqs, H, d,
+                                            ctx_max, scale, dt, 0, ctx->run.rows_lists_ready, ctx->run.extend_scratch, ctx->run.extend_scratch_bytes, pages, s));
+        else
+            RUN(vcla_attn_extend_rows(w.qkv, kc, vc, ctx->rope_cos, ctx->rope_sin, w.ao, ctx->run.rows_seqs, ctx->run.rows_n, T, ctx->run.cache_seqs, H, d,
+                                      ctx_max, scale, dt, 0, ctx->run.rows_lists_ready, ctx->run.extend_scratch, ctx->run.extend_scratch_bytes, s));
         ctx->run.rows_lists_ready = true;
     } else if (ctx->run.extend) {
         // a session's new block: RoPE + KV append + causal attention over the cache in one launch, keys split over workgroups
@@ -1160,8 +1169,10 @@ extern "C" size_t vcla_llama_extend_rows_workspace_bytes(const vcla_ctx* ctx, in
     return carve_extend_rows(ctx, M, n_seqs, nullptr, nullptr, nullptr, nullptr, nullptr);
 }
 
-extern "C" int vcla_llama_extend_rows(vcla_ctx* ctx, const void* inputs_embeds, const vcla_extend_seq* seqs, int n_seqs, void* kv_cache, int B_slots,
-                                      int ctx_max, float* logits, void* ws, size_t ws_bytes, void* stream) {
+// pages (vcla_llama_extend_rows_paged): kv_cache is a pool of 16-row blocks behind a block table in device memory, ctx_max the logical cap of a
+// slot; the kernel route only, checked before anything is launched
+static int llama_extend_rows_impl(vcla_ctx* ctx, const void* inputs_embeds, const vcla_extend_seq* seqs, int n_seqs, void* kv_cache, int B_slots,
+                                  int ctx_max, float* logits, void* ws, size_t ws_bytes, const vcla_kv_pages* pages, void* stream) {
     VCLA_KNOBS_SCOPE();
     VCLA_REQUIRE(ctx && ctx->finalized && ctx->c.t_layers > 0, VCLA_ERR_BAD_ARG, "llama_extend_rows: context not finalized, or vision-only");
     VCLA_REQUIRE(inputs_embeds && seqs && kv_cache && logits && ws, VCLA_ERR_BAD_ARG, "llama_extend_rows: null pointer");
@@ -1183,6 +1194,18 @@ extern "C" int vcla_llama_extend_rows(vcla_ctx* ctx, const void* inputs_embeds, 
     }
     VCLA_REQUIRE(ws_bytes >= vcla_llama_extend_rows_workspace_bytes(ctx, M, n_seqs, ctx_max), VCLA_ERR_WORKSPACE,
                  "llama_extend_rows: workspace %zu < %zu bytes", ws_bytes, vcla_llama_extend_rows_workspace_bytes(ctx, M, n_seqs, ctx_max));
+    if (pages) {
+        const int hd = c.t_hidden / c.t_heads;
+        VCLA_REQUIRE(c.act_dtype == VCLA_BF16, VCLA_ERR_BAD_DTYPE, "llama_extend_rows_paged: the paged pass is bf16 only (the fp32 route has no paged prefill)");
+        VCLA_REQUIRE(hd == 64 || hd == 128, VCLA_ERR_BAD_SHAPE, "llama_extend_rows_paged: head dim %d not in {64,128}", hd);
+        for (int i = 0; i < n_seqs; ++i)
+            VCLA_REQUIRE(seqs[i].rows <= VCLA_EXTEND_MAX_ROWS, VCLA_ERR_BAD_SHAPE, "llama_extend_rows_paged: block %d: %d rows (at most %d; a longer block has no paged route)",
+                         i, seqs[i].rows, VCLA_EXTEND_MAX_ROWS);
+        VCLA_REQUIRE(pages->table && pages->n_blocks >= 1 && (int64_t)pages->ld * VCLA_KV_BLOCK_ROWS >= ctx_max, VCLA_ERR_BAD_ARG,
+                     "llama_extend_rows_paged: a null block table, an empty pool, or a table row of %d blocks under ctx_max %d", pages->ld, ctx_max);
+        VCLA_REQUIRE((int64_t)pages->n_blocks * VCLA_KV_BLOCK_ROWS * hd * 2 < ((int64_t)1 << 32), VCLA_ERR_BAD_SHAPE,
+                     "llama_extend_rows_paged: n_blocks=%d: a head's slab must stay below 4 GiB", pages->n_blocks);
+    }
     hipStream_t s = (hipStream_t)stream;
     const size_t e = esz(ctx);
     const int D = c.t_hidden, H = c.t_heads, d = D / H;
@@ -1196,6 +1219,7 @@ extern "C" int vcla_llama_extend_rows(vcla_ctx* ctx, const void* inputs_embeds, 
     const RunScope scope(ctx);
     ctx->run.q8_ws = w.q8; ctx->run.q8s_ws = w.q8s;
     ctx->run.cache_seqs = B_slots;
+    ctx->run.pages = pages;                // llama_layer's `rows` mode takes the slab stride from the pool and calls the paged attention
     auto gamma_after = [&](int l) { return l + 1 < c.t_layers ? ctx->llama[l + 1].ln1g : nullptr; };
     if (rows_kernel_ok(ctx, seqs, n_seqs)) {
         ctx->run.rows_seqs = seqs;
@@ -1226,6 +1250,16 @@ extern "C" int vcla_llama_extend_rows(vcla_ctx* ctx, const void* inputs_embeds, 
         }
     }
     return gemm(ctx, s, hl, D, ctx->lm_head, nullptr, nullptr, 0, logits, c.t_vocab, n_seqs, c.t_vocab, D, VCLA_EPI_NONE, 1);
+}
+
+extern "C" int vcla_llama_extend_rows(vcla_ctx* ctx, const void* inputs_embeds, const vcla_extend_seq* seqs, int n_seqs, void* kv_cache, int B_slots,
+                                      int ctx_max, float* logits, void* ws, size_t ws_bytes, void* stream) {
+    return llama_extend_rows_impl(ctx, inputs_embeds, seqs, n_seqs, kv_cache, B_slots, ctx_max, logits, ws, ws_bytes, nullptr, stream);
+}
+
+extern "C" int vcla_llama_extend_rows_paged(vcla_ctx* ctx, const void* inputs_embeds, const vcla_extend_seq* seqs, int n_seqs, void* kv_cache, int B_slots,
+                                            int ctx_max, float* logits, void* ws, size_t ws_bytes, const vcla_kv_pages* pages, void* stream) {
+    return llama_extend_rows_impl(ctx, inputs_embeds, seqs, n_seqs, kv_cache, B_slots, ctx_max, logits, ws, ws_bytes, pages, stream);
 }
 
 // The persistent decode step serves B = 1 in the bf16 mode when its weight stream is registered, no fp8 decode copies are loaded (those

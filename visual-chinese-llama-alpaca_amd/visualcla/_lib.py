@@ -253,12 +253,18 @@ def kv_pages(table: torch.Tensor, n_blocks: int) -> KvPages:
     return a
 
 
-def kv_page_rows(rows, rows_needed, n_blocks: int, ld: int, owned=()) -> torch.Tensor:
+def kv_page_rows(rows, rows_needed, n_blocks: int, ld: int, owned=(), shared=None) -> torch.Tensor:
     """per-slot block lists -> int32 host tensor [len(rows), ld], every row its blocks in logical order and -1 behind them (rows of the
     table of vcla_attn_decode_paged).  The launcher cannot check a table in device memory: entries inside [0, n_blocks), no block owned
     twice -- among these rows or with `owned`, the blocks of the slots that stay live -- and enough blocks for the rows_needed[k] rows
-    slot k will write are checked HERE, before the upload; ValueError names the row."""
+    slot k will write are checked HERE, before the upload; ValueError names the row.
+    shared (share_blocks=True; None: nothing changes): shared[k] lists the leading blocks row k holds by reference, the first
+    len(shared[k]) = P_k / 16 entries of rows[k], which the slot only reads.  `owned` may then be a dict block -> logical index (a block
+    the live slots or the entries hold by reference) or -1 (a block somebody writes).  A block may stand in several rows, and in `owned`,
+    only at the SAME logical index, listed as shared by each row and below each one's P_k / 16; a block somebody writes has one holder."""
     out = torch.full((len(rows), ld), -1, dtype=torch.int32)
+    if shared is not None:
+        return _kv_page_rows_shared(out, rows, rows_needed, n_blocks, ld, owned, shared)
     seen = set(int(b) for b in owned)
     for k, (blocks, need) in enumerate(zip(rows, rows_needed)):
         blocks = [int(b) for b in blocks]
@@ -272,6 +278,38 @@ def kv_page_rows(rows, rows_needed, n_blocks: int, ld: int, owned=()) -> torch.T
             if b in seen:
                 raise ValueError(f"kv table row {k}: block {b} is owned twice")
             seen.add(b)
+        out[k, :len(blocks)] = torch.tensor(blocks, dtype=torch.int32)
+    return out
+
+
+def _kv_page_rows_shared(out, rows, rows_needed, n_blocks: int, ld: int, owned, shared) -> torch.Tensor:
+    """kv_page_rows with shared leading blocks.  `owned`: a dict block -> logical index (a block held by reference elsewhere: a live
+    slot's shared block, an entry's) or -1 (a block somebody writes), or a plain collection (all written)."""
+    if len(shared) != len(rows):
+        raise ValueError(f"kv table: {len(shared)} shared lists for {len(rows)} rows")
+    where = {int(b): int(j) for b, j in owned.items()} if hasattr(owned, "items") else {int(b): -1 for b in owned}
+    for k, (blocks, need, sh) in enumerate(zip(rows, rows_needed, shared)):
+        blocks, sh = [int(b) for b in blocks], [int(b) for b in sh]
+        if len(blocks) > ld:
+            raise ValueError(f"kv table row {k}: {len(blocks)} blocks for a table of {ld} per slot")
+        if len(blocks) * KV_BLOCK_ROWS < int(need):
+            raise ValueError(f"kv table row {k}: {len(blocks)} blocks of {KV_BLOCK_ROWS} rows for the {int(need)} rows the slot will write")
+        if blocks[:len(sh)] != sh:
+            raise ValueError(f"kv table row {k}: the shared blocks {sh} are not the first {len(sh)} entries of the row")
+        if len(set(blocks)) != len(blocks):
+            raise ValueError(f"kv table row {k}: a block stands twice in the row")
+        for j, b in enumerate(blocks):
+            if not 0 <= b < n_blocks:
+                raise ValueError(f"kv table row {k}: block {b} outside the pool of {n_blocks}")
+            if j < len(sh):                                      # read only: may be held elsewhere, by reference, at the same index
+                if b in where and where[b] != j:
+                    raise ValueError(f"kv table row {k}: shared block {b} at logical index {j} is "
+                                     + ("written by another holder" if where[b] < 0 else f"held at logical index {where[b]} elsewhere"))
+                where[b] = j
+            else:                                                # the slot writes it: one holder
+                if b in where:
+                    raise ValueError(f"kv table row {k}: block {b} is owned twice" + (" (it is shared elsewhere and this row would write it)" if where[b] >= 0 else ""))
+                where[b] = -1
         out[k, :len(blocks)] = torch.tensor(blocks, dtype=torch.int32)
     return out
 
@@ -472,6 +510,8 @@ SYMBOLS = {
     "vcla_attn_decode_paged": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, C.POINTER(KvPages), _vp, _i64, _f, _i, _i, _vp]),
     "vcla_llama_decode_slots_paged": (_i, [_vp, C.POINTER(SlotArgs), _i, _vp, _i, _vp, _vp, _sz, _i, C.POINTER(SampleArgs), _vp, _vp,
                                            C.POINTER(LogprobArgs), C.POINTER(ConstrainArgs), C.POINTER(StopArgs), C.POINTER(KvPages), _vp]),
+    "vcla_attn_extend_rows_paged": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _i, _i, _vp, _sz, C.POINTER(KvPages), _vp]),
+    "vcla_llama_extend_rows_paged": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _sz, C.POINTER(KvPages), _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -79,6 +79,17 @@ def check_kv_pool_tokens(kv_pool_tokens) -> Optional[int]:
     return (int(kv_pool_tokens) + KV_BLOCK_ROWS - 1) // KV_BLOCK_ROWS
 
 
+def check_share_blocks(share_blocks, kv_pool_tokens) -> bool:
+    """the `share_blocks` argument of generate_many / chat_many: a bool (absent = False), and True only beside kv_pool_tokens"""
+    if share_blocks is None:
+        return False
+    if not isinstance(share_blocks, bool):
+        raise ValueError(f"share_blocks must be a bool (got {share_blocks!r})")
+    if share_blocks and kv_pool_tokens is None:
+        raise ValueError("share_blocks=True needs kv_pool_tokens (it shares blocks of the paged K/V pool; without a pool, share_prefix=True copies the rows)")
+    return share_blocks
+
+
 def blocks_for(rows: int) -> int:
     """blocks of KV_BLOCK_ROWS rows that hold `rows` rows"""
     return (int(rows) + KV_BLOCK_ROWS - 1) // KV_BLOCK_ROWS
@@ -86,7 +97,9 @@ def blocks_for(rows: int) -> int:
 
 class KvBlockAllocator:
     """The blocks 0 .. n_blocks - 1 of a paged K/V pool, host only: alloc(n) hands out n free blocks or None (and
-    then takes nothing), free(list) takes them back; a double free or a block that was never handed out raises.  used / peak count blocks."""
+    then takes nothing), free(list) takes them back; a double free or a block that was never handed out raises.  used / peak count blocks.
+    Reference counts (section 7l): alloc gives a block its first HOLDER, retain(list) adds one to blocks that are out, free(list) drops one
+    and the block returns to the free stack with its last; holders(b) / shared count them."""
 
     def __init__(self, n_blocks: int):
         if isinstance(n_blocks, bool) or not isinstance(n_blocks, int) or n_blocks < 1:
@@ -94,7 +107,9 @@ class KvBlockAllocator:
         self.n_blocks = n_blocks
         self._free = list(range(n_blocks - 1, -1, -1))           # a stack: alloc pops from the end, a freed block is reused first
         self._out = set()
+        self._extra: Dict[int, int] = {}                         # block -> holders beyond the first (absent: one holder)
         self.peak = 0
+        self.shared_peak = 0                                     # most blocks that had more than one holder at once
 
     @property
     def used(self) -> int:
@@ -114,13 +129,37 @@ class KvBlockAllocator:
         self.peak = max(self.peak, len(self._out))
         return got
 
+    def retain(self, blocks) -> None:
+        """one more holder for every block of the list (each at most once); a block that is not out raises and nothing is retained"""
+        blocks = [int(b) for b in blocks]
+        bad = [b for b in blocks if b not in self._out]
+        if bad or len(set(blocks)) != len(blocks):
+            raise ValueError(f"KvBlockAllocator.retain: blocks {sorted(set(bad)) or blocks} are not allocated (or named twice)")
+        for b in blocks:
+            self._extra[b] = self._extra.get(b, 0) + 1
+        self.shared_peak = max(self.shared_peak, len(self._extra))
+
+    def holders(self, b: int) -> int:
+        return 1 + self._extra.get(int(b), 0) if int(b) in self._out else 0
+
+    @property
+    def shared(self) -> int:
+        """blocks with more than one holder"""
+        return len(self._extra)
+
     def free(self, blocks) -> None:
         blocks = [int(b) for b in blocks]
         bad = [b for b in blocks if b not in self._out]
         if bad or len(set(blocks)) != len(blocks):
             raise ValueError(f"KvBlockAllocator.free: blocks {sorted(set(bad)) or blocks} are not allocated (a double free, or a block of another pool)")
-        self._out.difference_update(blocks)
-        self._free.extend(blocks)
+        for b in blocks:                                         # one holder less; the last one returns the block
+            if b in self._extra:
+                self._extra[b] -= 1
+                if not self._extra[b]:
+                    del self._extra[b]
+            else:
+                self._out.discard(b)
+                self._free.append(b)
 
 
 def stop_hit(tokens: Sequence[int], seqs) -> bool:
@@ -206,15 +245,30 @@ class InflightScheduler:
     Requests are still taken in arrival order; request i is admitted at a boundary only if, after it joins its group (whose T may grow, which
     raises every member's need), the blocks of all groups of the boundary fit the free ones -- otherwise admission ends there with i at
     the head of the queue.  A request that alone needs more blocks than the pool holds is refused up front, so the head always fits once
-    no slot is live.  Not beside share_prefix."""
+    no slot is live.  Not beside share_prefix.
+
+    block_plan (share_blocks=True; a prefix.plan(..., block_rows=16) of the queue, needs kv_pool_tokens): admission is
+    ragged as under share_prefix -- one group per boundary, nobody padded, request i decodes from its own T_i -- and the leading P_i / 16
+    blocks of request i's table row are its source entry's blocks, RETAINED, not copied; it allocates ceil((T_i + budget_i) / 16) -
+    P_i / 16 blocks of its own.  A creator's leading blocks gain its entry as a second holder (entry_blocks[c]); the entry drops its hold
+    at the end of the admission that takes its last planned reader, live slots keep what they read, a harvested request frees its whole
+    row.  A block with more than one holder is never written: every holder's first written row is >= its P_i (a creator's rows lie in
+    front of its T_c, where it decodes).  Gate: arrival order; the head is admitted if the OWN blocks of everyone admitted at this boundary
+    fit the free ones.  Blocks held by entries alone never exceed entry_bound = ceil(min(plan.pool_rows, plan.peak_pool_rows) / 16); a
+    request whose full need plus that bound exceeds the pool is refused up front (all of them in one message), so the head always fits
+    once no slot is live.  stats gain kv_rows_shared and kv_blocks_shared_peak."""
 
     def __init__(self, prompt_lens: Sequence[int], budgets: Sequence[int], has_image: Sequence[bool], max_batch: int,
                  max_position_embeddings: int, image_at_head: bool = False, steps_per_sync: int = 8, share_prefix: bool = False,
                  logprobs: Optional[int] = None, targets: Optional[Sequence[Optional[Sequence[int]]]] = None,
-                 stops: Optional[Sequence[Optional[Sequence[Sequence[int]]]]] = None, kv_pool_tokens: Optional[int] = None):
+                 stops: Optional[Sequence[Optional[Sequence[Sequence[int]]]]] = None, kv_pool_tokens: Optional[int] = None, block_plan=None):
         pool_blocks = check_kv_pool_tokens(kv_pool_tokens)
         if pool_blocks is not None and share_prefix:
             raise ValueError("kv_pool_tokens with share_prefix=True (the ragged admission pass needs a paged vcla_attn_extend_rows)")
+        if block_plan is not None and (pool_blocks is None or image_at_head):
+            raise ValueError("share_blocks=True needs kv_pool_tokens" if pool_blocks is None else "share_blocks=True with image_at_head=True")
+        if block_plan is not None and (block_plan.block_rows != KV_BLOCK_ROWS or len(block_plan.T) != len(prompt_lens)):
+            raise ValueError(f"share_blocks: the plan must be made at block_rows={KV_BLOCK_ROWS} for the {len(prompt_lens)} requests of the queue")
         if max_batch < 1:
             raise ValueError(f"max_batch must be at least 1 (got {max_batch})")
         if steps_per_sync < 1:
@@ -247,6 +301,8 @@ class InflightScheduler:
         self.steps_per_sync = int(steps_per_sync)
         self.image_at_head = bool(image_at_head)
         self.share_prefix = bool(share_prefix)
+        self.block_plan = block_plan
+        self.ragged = self.share_prefix or block_plan is not None
         self.cap = max(self.budget, default=1)                   # rows of the history / uniforms buffers
         self.ctx_max = min(self.max_pos, round_up(max(self.T, default=0) + self.cap, 64))
         self.queue = deque(range(self.n))
@@ -261,14 +317,20 @@ class InflightScheduler:
         self.pool: Optional[KvBlockAllocator] = None
         self.blocks: Dict[int, List[int]] = {}                   # paged: running request -> the pool blocks it reserved, in logical order
         if pool_blocks is not None:
-            big = [i for i in range(self.n) if blocks_for(self.T[i] + self.budget[i]) > pool_blocks]
+            self.entry_bound = blocks_for(min(block_plan.pool_rows, block_plan.peak_pool_rows)) if block_plan is not None else 0
+            big = [i for i in range(self.n) if blocks_for(self.T[i] + self.budget[i]) + self.entry_bound > pool_blocks]
             if big:
                 raise ValueError(f"kv_pool_tokens={kv_pool_tokens}: a pool of {pool_blocks} blocks of {KV_BLOCK_ROWS} rows cannot hold request "
-                                 + ", ".join(f"{i} ({self.T[i]} + {self.budget[i]} rows = {blocks_for(self.T[i] + self.budget[i])} blocks)" for i in big))
+                                 + ", ".join(f"{i} ({self.T[i]} + {self.budget[i]} rows = {blocks_for(self.T[i] + self.budget[i])} blocks)" for i in big)
+                                 + (f" beside the {self.entry_bound} blocks shared prefixes may hold (share_blocks=True)" if block_plan is not None else ""))
             self.pool = KvBlockAllocator(pool_blocks)
             self._waited = False                                 # this boundary is already counted in admission_waits_blocks
             self._rows_reserved = 0
             self.stats.update(kv_pool_blocks=pool_blocks, kv_blocks_peak=0, kv_rows_reserved_peak=0, admission_waits_blocks=0)
+            if block_plan is not None:
+                self.entry_blocks: Dict[int, List[int]] = {}     # creator -> the blocks its entry holds (the creator's leading blocks)
+                self._res: Dict[int, int] = {}                   # running request -> the rows it reserved for itself
+                self.stats.update(kv_rows_shared=0, kv_blocks_shared_peak=0)
 
     # ------------------------------------------------------------------ admission
     def free_slots(self) -> List[int]:
@@ -287,13 +349,15 @@ class InflightScheduler:
         groups: List[Group] = []
         if self.pool is not None and self._waited and self.running:
             return groups                                        # the head waits for blocks: admission of this boundary has ended
+        if self.block_plan is not None:
+            return self._admit_shared(free_slots)
         for b in sorted(free_slots):
             if not self.queue:
                 break
             if self.slot_req[b] is not None:
                 raise ValueError(f"slot {b} still holds request {self.slot_req[b]}")
             i = self.queue[0]
-            if self.share_prefix:
+            if self.ragged:
                 g = groups[0] if groups else None                # T_i + budget_i <= ctx_max holds for every request by construction
             else:
                 g = next((g for g in groups if self._fits(g, i)), None)
@@ -304,7 +368,7 @@ class InflightScheduler:
                 break
             self.queue.popleft()
             if g is None:
-                g = Group(image=self.has_image[i], ragged=self.share_prefix)
+                g = Group(image=self.has_image[i], ragged=self.ragged)
                 groups.append(g)
             g.requests.append(i)
             g.slots.append(b)
@@ -324,6 +388,77 @@ class InflightScheduler:
             self.stats["kv_rows_reserved_peak"] = max(self.stats["kv_rows_reserved_peak"], self._rows_reserved)
         self.stats["admission_groups"] += len(groups)
         return groups
+
+    def _admit_shared(self, free_slots: Sequence[int]) -> List[Group]:
+        """admit() under a block plan: one ragged group; the table rows of its requests are assembled here (shared blocks retained, own
+        blocks allocated), in arrival order so that a creator's entry exists before its readers of the same boundary take it"""
+        pl, g, need = self.block_plan, Group(ragged=True), 0
+        for b in sorted(free_slots):
+            if not self.queue:
+                break
+            if self.slot_req[b] is not None:
+                raise ValueError(f"slot {b} still holds request {self.slot_req[b]}")
+            i = self.queue[0]
+            own = blocks_for(self.T[i] + self.budget[i]) - pl.P[i] // KV_BLOCK_ROWS
+            if need + own > self.pool.available:
+                if not self._waited:                             # a free slot stays empty: the head of the queue waits for blocks
+                    self.stats["admission_waits_blocks"] += 1
+                    self._waited = True
+                break
+            need += own
+            self.queue.popleft()
+            g.requests.append(i)
+            g.slots.append(b)
+            g.T = max(g.T, self.T[i])
+            g.image = g.image or self.has_image[i]
+            self.slot_req[b] = i
+        if not g.requests:
+            return []
+        for i in g.requests:
+            self.decode_from[i] = self.T[i]
+            lead = []
+            if pl.P[i] > 0:                                      # by reference: one more holder, no copy
+                lead = self.entry_blocks[pl.source[i]][:pl.P[i] // KV_BLOCK_ROWS]
+                self.pool.retain(lead)
+                self.stats["kv_rows_shared"] += pl.P[i]
+            own = self.pool.alloc(blocks_for(self.T[i] + self.budget[i]) - len(lead))
+            if own is None:
+                raise ValueError(f"request {i}: the pool ran out of blocks behind the admission gate")
+            self.blocks[i] = lead + own
+            self._res[i] = self.T[i] + self.budget[i] - pl.P[i]
+            self._rows_reserved += self._res[i]
+            e = pl.entries.get(i)
+            if e is not None and e.rows > 0:                     # its leading blocks gain the entry as a second holder
+                self.entry_blocks[i] = self.blocks[i][:e.rows // KV_BLOCK_ROWS]
+                self.pool.retain(self.entry_blocks[i])
+        for i in g.requests:                                     # an entry whose last planned reader was admitted here drops its hold
+            s = pl.source[i]
+            if s is not None and pl.entries[s].last_reader == i:
+                self.pool.free(self.entry_blocks.pop(s))
+        self.stats["kv_blocks_peak"] = self.pool.peak
+        self.stats["kv_blocks_shared_peak"] = self.pool.shared_peak
+        self.stats["kv_rows_reserved_peak"] = max(self.stats["kv_rows_reserved_peak"], self._rows_reserved)
+        self.stats["admission_groups"] += 1
+        return [g]
+
+    def page_rows(self, members: Sequence[int], pending: Sequence[int] = ()):
+        """block plan: the arguments of _lib.kv_page_rows for the table rows of `members` (requests admitted and about to be prefilled) ->
+        (rows, rows needed, shared lists, owned).  shared[k]: the leading P_i / 16 blocks, held by reference.  owned: every block of the other
+        running requests (`pending`, admitted but prefilled in a later pass, left out) and of the entries -> its logical index when it has
+        more than one holder (read only, may be named again at that index), -1 when somebody writes it."""
+        pl = self.block_plan
+        skip = set(members) | set(pending)
+        owned: Dict[int, int] = {}
+        for j, bl in self.blocks.items():
+            if j not in skip:
+                for idx, b in enumerate(bl):
+                    owned[b] = idx if self.pool.holders(b) > 1 else -1
+        for c, bl in self.entry_blocks.items():
+            if c not in skip:
+                for idx, b in enumerate(bl):
+                    owned.setdefault(b, idx)
+        return ([self.blocks[i] for i in members], [self.T[i] + self.budget[i] for i in members],
+                [self.blocks[i][:pl.P[i] // KV_BLOCK_ROWS] for i in members], owned)
 
     def _blocks_needed(self, groups: List[Group], g: Optional[Group], i: int) -> int:
         """blocks the groups of this boundary reserve once request i has joined group g (None: a group of its own)"""
@@ -347,7 +482,7 @@ class InflightScheduler:
         self.slot_req[b] = None
         if self.pool is not None:                                # harvested (finished, stopped or cancelled): the reservation returns
             self.pool.free(self.blocks.pop(i))
-            self._rows_reserved -= self.decode_from[i] + self.budget[i]
+            self._rows_reserved -= self._res.pop(i) if self.block_plan is not None else self.decode_from[i] + self.budget[i]
 
     def cancel(self, b: int, tokens: Sequence[int], extra=None) -> None:
         """The callback cancelled slot b's request at this boundary: it is complete with the tokens delivered so far (extra: their
@@ -456,18 +591,18 @@ def static_batch_steps(budgets: Sequence[int], slots: int) -> int:
 def simulate(budgets: Sequence[int], slots: int, steps_per_sync: int, eos_at: Optional[Dict[int, int]] = None, prompt_lens=None, has_image=None,
              max_position_embeddings: int = 1 << 20, image_at_head: bool = False, share_prefix: bool = False, logprobs: Optional[int] = None,
              targets=None, stops=None, on_tokens: Optional[Callable] = None, token_of: Optional[Callable[[int, int], int]] = None,
-             kv_pool_tokens: Optional[int] = None, watch: Optional[Callable] = None):
+             kv_pool_tokens: Optional[int] = None, watch: Optional[Callable] = None, block_plan=None):
     """Drives a scheduler with the host model of the slot step and a stepper that emits token (request, k) = 1000 * request + k, or the
     eos id 0 as request i's eos_at[i]-th token.  Returns (scheduler, log of (boundary, slot, request) admissions).
     logprobs / targets: the scheduler's; a forced request emits its targets instead, and token t of request i scores
     -(i + t / 1000) with top ids [t * 10 + r] and top logprobs [-(i + r)] (a stand-in for the device buffers).
     stops: the scheduler's (per request); the slot table carries them as the device table does.  on_tokens: the streaming callback of
     generate_many, called as the slots loop calls it; a true return value cancels.  token_of(i, k): request i's k-th token (1-based)
-    instead of 1000 * (i + 1) + k.  kv_pool_tokens: the scheduler's; watch(scheduler) is called after every admission."""
+    instead of 1000 * (i + 1) + k.  kv_pool_tokens / block_plan: the scheduler's; watch(scheduler) is called after every admission."""
     n = len(budgets)
     eos_at = eos_at or {}
     sch = InflightScheduler(prompt_lens or [4] * n, budgets, has_image or [False] * n, slots, max_position_embeddings, image_at_head, steps_per_sync,
-                            share_prefix, logprobs, targets, stops, kv_pool_tokens)
+                            share_prefix, logprobs, targets, stops, kv_pool_tokens, block_plan)
     B = sch.slots
     use_stops = any(x is not None for x in sch.stops)
     slot_stops: List[List[List[int]]] = [[] for _ in range(B)]

@@ -207,7 +207,7 @@ class TextStops:
 
 @torch.inference_mode()
 def chat_many(model, items, generation_config=None, max_batch=64, share_prefix=False, generation_configs=None, seeds=None, prefix_cache=None,
-              logprobs=None, constraints=None, stop=None, stops=None, on_text=None, kv_pool_tokens=None):
+              logprobs=None, constraints=None, stop=None, stops=None, on_text=None, kv_pool_tokens=None, share_blocks=False):
     """The bulk form of chat(): items = [(image, text) or (image, text, history), ...] -> [(response, history), ...].  Every prompt is built as
     chat() builds it, the queue is answered by model.generate_many (in-flight batching over max_batch slots) and every response is appended
     to its item's history exactly as chat() appends it.  share_prefix: generate_many's switch -- the system prompt every item begins with and the
@@ -228,11 +228,14 @@ def chat_many(model, items, generation_config=None, max_batch=64, share_prefix=F
     `stop_sequences`: a sentencepiece tokenisation depends on context, so no token sequence stands for a string.
     on_text=fn: the streamed form, fn(i, text_so_far, finished) once per boundary for every item that produced tokens, text_so_far
     already cut at a stop string; exactly one call per item has finished=True and it is the last.
-    kv_pool_tokens=n (generate_many's; None: nothing changes): the slots share a paged K/V pool of ceil(n / 16) blocks of 16 rows."""
+    kv_pool_tokens=n (generate_many's; None: nothing changes): the slots share a paged K/V pool of ceil(n / 16) blocks of 16 rows.
+    share_blocks=True (generate_many's, needs kv_pool_tokens): the pool's form of share_prefix -- the leading full 16-row blocks items have in
+    common (the system prompt, the image slot of items about one image) are stored once and named by every item's block table."""
     from . import constraints as _constraints
-    from .inflight import check_kv_pool_tokens, check_logprobs
+    from .inflight import check_kv_pool_tokens, check_logprobs, check_share_blocks
     logprobs = check_logprobs(logprobs)
     check_kv_pool_tokens(kv_pool_tokens)
+    share_blocks = check_share_blocks(share_blocks, kv_pool_tokens)
     if constraints is not None:
         constraints = _constraints.from_items(constraints, len(items))
     for name, lst in (("generation_configs", generation_configs), ("seeds", seeds)):
@@ -263,6 +266,7 @@ def chat_many(model, items, generation_config=None, max_batch=64, share_prefix=F
                                **({} if prefix_cache is None else dict(prefix_cache=prefix_cache)),
                                **({} if logprobs is None else dict(logprobs=logprobs)),
                                **({} if kv_pool_tokens is None else dict(kv_pool_tokens=kv_pool_tokens)),
+                               **(dict(share_blocks=True) if share_blocks else {}),
                                **(dict(on_tokens=text_stops.on_tokens) if text_stops.active else {}))
     results = []
     for i, (out, history) in enumerate(zip(outs, histories)):

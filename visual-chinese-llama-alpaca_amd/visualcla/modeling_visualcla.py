@@ -629,15 +629,27 @@ class VisualCLAModel:
         cache.length = pos0 + Tn
         return logits
 
-    def _extend_rows(self, embeds: torch.Tensor, table, kv: torch.Tensor, ws_for=None):
+    def _extend_rows(self, embeds: torch.Tensor, table, kv: torch.Tensor, ws_for=None, pages=None, ctx_max: Optional[int] = None):
         """the decoder over the new rows of several requests in one pass (vcla_llama_extend_rows): embeds [M, D], the
         blocks of `table` = [(slot, pos, rows), ...] packed back to back; kv [L, 2, B_slots, H, ctx_max, d], block i is appended to its slot
         at [pos, pos + rows) -> the last-row logits of every block, [len(table), V].  ws_for = (rows, blocks): size the workspace for passes up
-        to that size (one allocation for a whole queue)."""
+        to that size (one allocation for a whole queue).
+        pages (a vcla_kv_pages over a device table int32 [B_slots, ld], with ctx_max the logical cap of a slot): kv is the pool
+        [L, 2, H, n_blocks * 16, d] and the pass is vcla_llama_extend_rows_paged -- the kernel route only."""
         lib = _lib.load()
         seqs, M = _lib.extend_seqs(table)
         if embeds.dim() != 2 or embeds.shape[0] != M:
             raise ValueError(f"_extend_rows: {tuple(embeds.shape)} embeddings for blocks of {M} rows")
+        if pages is not None:
+            n = len(table)
+            logits = torch.empty(n, self.config.text_config["vocab_size"], dtype=torch.float32, device=self._device)
+            cap_m, cap_n = ws_for if ws_for is not None else (M, n)
+            ws = self._buf("extend_rows", lib.vcla_llama_extend_rows_workspace_bytes(self._ctx, max(M, cap_m), max(n, cap_n), int(ctx_max)))
+            embeds = embeds.contiguous()
+            with torch.cuda.device(self._device):
+                _lib.check(lib.vcla_llama_extend_rows_paged(self._ctx, embeds.data_ptr(), seqs, n, kv.data_ptr(), int(pages.table.shape[0]), int(ctx_max),
+                                                            logits.data_ptr(), ws.data_ptr(), ws.numel(), C.byref(pages.args), _lib.stream_ptr()))
+            return logits
         n, B_slots, ctx_max = len(table), kv.shape[2], kv.shape[4]
         logits = torch.empty(n, self.config.text_config["vocab_size"], dtype=torch.float32, device=self._device)
         cap_m, cap_n = ws_for if ws_for is not None else (M, n)
@@ -1180,10 +1192,11 @@ class VisualCLAModel:
     # ------------------------------------------------------------------ in-flight batching
     @staticmethod
     def _refuse_inflight_conflicts(gc, vocab_size: int = 0, kv_fp8: bool = False, max_budget: int = 0, leftover_kwargs: Optional[dict] = None,
-                                   share_prefix: bool = False, image_at_head: bool = False, masked_requests=()) -> None:
+                                   share_prefix: bool = False, image_at_head: bool = False, masked_requests=(), share_name: str = "share_prefix=True") -> None:
         """generate_many decodes on the device-resident slots loop (argmax or the device sampler, one floor for the whole queue): every setting
         that needs more is refused by name, all of them in one message.  Needs no device.  share_prefix=True places every prompt un-padded
-        at position 0 of its slot: it also refuses image_at_head=True and the requests (`masked_requests`, by index) whose attention_mask has a zero."""
+        at position 0 of its slot: it also refuses image_at_head=True and the requests (`masked_requests`, by index) whose attention_mask has a zero
+        (share_name: the argument the message names -- share_blocks=True refuses the same)."""
         from types import SimpleNamespace
         from .logits_processors import _HOST_ONLY_FIELDS, min_token_floor, needs_host_processors, refuse_unsupported
         refuse_unsupported(gc, leftover_kwargs)
@@ -1216,9 +1229,9 @@ class VisualCLAModel:
         if kv_fp8:
             bad.append("the e4m3 K/V cache (enable_fp8_decode(kv_cache=True))")
         if share_prefix and image_at_head:
-            bad.append("share_prefix=True with image_at_head=True")
+            bad.append(f"{share_name} with image_at_head=True")
         if share_prefix and len(masked_requests):
-            bad.append("share_prefix=True with an attention_mask that masks positions (request " + ", ".join(str(i) for i in masked_requests) + ")")
+            bad.append(f"{share_name} with an attention_mask that masks positions (request " + ", ".join(str(i) for i in masked_requests) + ")")
         if bad:
             raise ValueError("generate_many (in-flight batching) cannot be combined with " + ", ".join(bad))
 
@@ -1337,7 +1350,7 @@ class VisualCLAModel:
 
     @staticmethod
     def _refuse_per_request_conflicts(configs, members, budgets, vocab_size: int = 0, kv_fp8: bool = False, share_prefix: bool = False,
-                                      image_at_head: bool = False, masked_requests=()) -> None:
+                                      image_at_head: bool = False, masked_requests=(), share_name: str = "share_prefix=True") -> None:
         """_refuse_inflight_conflicts for a queue whose requests carry their own configs: once per distinct config (`configs[c]` serves the
         requests `members[c]`, with the sampler limits taken against THEIR budgets), once for what belongs to the queue; ONE ValueError,
         grouped by reason, naming the requests (`request 3, 7: num_beams=2`).  Needs no device."""
@@ -1355,7 +1368,7 @@ class VisualCLAModel:
             def __getattr__(self, name):
                 return None
         try:
-            VisualCLAModel._refuse_inflight_conflicts(_Unset(), 0, kv_fp8, 0, None, share_prefix, image_at_head, masked_requests)
+            VisualCLAModel._refuse_inflight_conflicts(_Unset(), 0, kv_fp8, 0, None, share_prefix, image_at_head, masked_requests, share_name)
         except ValueError as e:
             parts.append(str(e)[len(head):])
         if parts:
@@ -1364,7 +1377,7 @@ class VisualCLAModel:
     @torch.no_grad()
     def generate_many(self, requests, max_batch: int = 64, generation_config=None, steps_per_sync: int = 8, use_graph: Optional[bool] = None,
                       share_prefix: bool = False, prefix_pool_tokens: Optional[int] = None, prefix_cache=None, logprobs: Optional[int] = None,
-                      on_tokens=None, kv_pool_tokens: Optional[int] = None, **kwargs):
+                      on_tokens=None, kv_pool_tokens: Optional[int] = None, share_blocks: bool = False, **kwargs):
         """In-flight batching over a queue: -> List[LongTensor [n_i]] in request order, the NEW tokens of every request, its eos included
         and nothing behind it.  requests: dicts with `input_ids` ([T] or [1, T]), optional `pixel_values`, `attention_mask`, `max_new_tokens`
         (default: the config's budget by generate()'s rules for that prompt), `generation_config`, `seed`.
@@ -1444,13 +1457,26 @@ class VisualCLAModel:
         ceil((T_group + budget) / 16) blocks when it is admitted and returns them when it is harvested; requests are admitted in
         arrival order, and the head of the queue waits at a boundary while its blocks do not fit.  Same results, bit for bit the
         same schedule whenever nothing waits.  A queue in which a request alone needs more blocks than the pool holds is refused up
-        front, naming the requests.  Not beside share_prefix / prefix_cache (the ragged admission pass has no paged form).  With it a
+        front, naming the requests.  Not beside share_prefix / prefix_cache: share_blocks=True (below) is the pool's form of prefix sharing.  With it a
         queue of one request (or max_batch=1) takes the slots route at one slot.  last_inflight_stats gains `kv_pool_blocks`,
         `kv_blocks_peak`, `kv_bytes` (the pool), `kv_bytes_contiguous` (what max_batch x ctx_max rows would have taken),
-        `kv_rows_reserved_peak`, `admission_waits_blocks` (boundaries at which a free slot stayed empty because the head did not fit)."""
-        from .inflight import InflightScheduler, RequestOutput, check_kv_pool_tokens, check_logprobs, check_stop_sequences
+        `kv_rows_reserved_peak`, `admission_waits_blocks` (boundaries at which a free slot stayed empty because the head did not fit).
+
+        share_blocks=True (needs kv_pool_tokens; False or absent: nothing changes): the pool's form of prefix sharing (DESIGN.md section
+        7l).  The plan of share_prefix is made at block granularity -- every shared length a multiple of 16 rows, the rows behind the
+        last full block recomputed -- and a request's leading P_i / 16 table entries NAME the blocks of its source: shared rows are stored
+        once and read by all, nothing is copied.  The admission pass is the ragged one, on the pool (vcla_llama_extend_rows_paged).  Same
+        results as without the argument: in fp32 the same ids; in bf16 under the terms of share_prefix (reused rows were computed in
+        another request's pass).  Refuses what share_prefix=True refuses (image_at_head=True, a mask with a zero, the e4m3 cache) and
+        prefix_cache.  A request whose blocks plus the blocks shared prefixes may hold alone (the plan's bound) exceed the pool is
+        refused up front.  last_inflight_stats carries share_prefix's counters (rows_reused, rows_computed, vision_runs,
+        admission_passes, rows_calls), the pool's, and `kv_rows_shared` (rows reused by reference), `kv_blocks_shared_peak`."""
+        from .inflight import InflightScheduler, RequestOutput, check_kv_pool_tokens, check_logprobs, check_share_blocks, check_stop_sequences
         from .prefix_cache import PrefixCache
         logprobs = check_logprobs(logprobs)                       # before anything else: the argument by name
+        share_blocks = check_share_blocks(share_blocks, kv_pool_tokens)
+        if share_blocks and prefix_cache is not None:
+            raise ValueError("generate_many: share_blocks=True with prefix_cache (a prefix cache on the pool is not built; its blocks live in a pool of their own)")
         if check_kv_pool_tokens(kv_pool_tokens) is not None and (share_prefix or prefix_cache is not None):
             raise ValueError(f"generate_many: kv_pool_tokens with {'prefix_cache' if prefix_cache is not None else 'share_prefix=True'} (the ragged admission "
                              "pass needs a paged vcla_attn_extend_rows, its fp32 route a paged prefill)")
@@ -1481,7 +1507,7 @@ class VisualCLAModel:
         lens = [int(r["ids"].numel()) + (Q if (self.image_at_head and r["px"] is not None) else 0) for r in reqs]
         budgets = self._request_budgets(gc, reqs, gcs, lens)
         masked = []
-        if share_prefix:
+        if share_prefix or share_blocks:
             with_mask = [i for i, r in enumerate(reqs) if r["am"] is not None]
             if with_mask:                                         # one copy back for the whole queue; an all-ones mask is no mask
                 lows = torch.stack([reqs[i]["am"].min() for i in with_mask]).tolist()
@@ -1489,13 +1515,15 @@ class VisualCLAModel:
         if len(class_gcs) == 1:                                   # one config for the whole queue (the queue's, or the one every request brought)
             self._refuse_inflight_conflicts(class_gcs[0], t["vocab_size"], bool(getattr(self, "_kv_fp8", False)),
                                             max((min(b, t["max_position_embeddings"]) for b in budgets), default=0), kwargs,
-                                            share_prefix=bool(share_prefix), image_at_head=bool(self.image_at_head), masked_requests=masked)
+                                            share_prefix=bool(share_prefix) or share_blocks, image_at_head=bool(self.image_at_head), masked_requests=masked,
+                                            share_name="share_blocks=True" if share_blocks else "share_prefix=True")
         else:
             from .logits_processors import refuse_unsupported
             refuse_unsupported(gc, kwargs)
             self._refuse_per_request_conflicts(class_gcs, [[i for i, c in enumerate(cls) if c == k] for k in range(len(class_gcs))],
                                                [min(b, t["max_position_embeddings"]) for b in budgets], t["vocab_size"],
-                                               bool(getattr(self, "_kv_fp8", False)), bool(share_prefix), bool(self.image_at_head), masked)
+                                               bool(getattr(self, "_kv_fp8", False)), bool(share_prefix) or share_blocks, bool(self.image_at_head), masked,
+                                               "share_blocks=True" if share_blocks else "share_prefix=True")
         extra_stats = dict(config_classes=len(class_gcs), sampler_rows=sum(self._uses_sampler(g) for g, tg in zip(gcs, targets) if tg is None),
                            seeded=sum(sd is not None for sd in seeds))
         if logprobs is not None:
@@ -1503,9 +1531,15 @@ class VisualCLAModel:
         ctable = self._constraint_table(reqs, gcs, t["vocab_size"])      # refusals by request index, and the caps, before any kernel runs
         if ctable is not None:
             extra_stats.update(ctable.stats())
+        block_plan = None
+        if share_blocks and reqs:                                 # the plan at block granularity, for min(max_batch, n) slots as the scheduler sizes them
+            if max_batch < 1:
+                raise ValueError(f"max_batch must be at least 1 (got {max_batch})")
+            block_plan = slots_run._prefix_plan(self, reqs, min(int(max_batch), len(reqs)), prefix_pool_tokens, block_rows=_lib.KV_BLOCK_ROWS)
         # raises for a prompt that leaves no room, by index, before any kernel runs
         sched = InflightScheduler(lens, budgets, [r["px"] is not None for r in reqs], max_batch, t["max_position_embeddings"], self.image_at_head,
-                                  steps_per_sync, share_prefix=bool(share_prefix), logprobs=logprobs, targets=targets, stops=stops, kv_pool_tokens=kv_pool_tokens)
+                                  steps_per_sync, share_prefix=bool(share_prefix), logprobs=logprobs, targets=targets, stops=stops, kv_pool_tokens=kv_pool_tokens,
+                                  block_plan=block_plan)
         slots_only = kv_pool_tokens is not None or prefix_cache is not None or logprobs is not None or ctable is not None or on_tokens is not None or any(x is not None for x in sched.stops)
         if use_graph is None:
             use_graph = os.environ.get("VCLA_DECODE_GRAPH", "1") != "0"
@@ -1533,7 +1567,7 @@ class VisualCLAModel:
                 self.last_inflight_stats.update(rows_reused=0, rows_computed=sum(lens), vision_runs=sum(r["px"] is not None for r in reqs), pool_entries=0,
                                                 pool_bytes=0)
             return out
-        plan = pstate = None
+        plan, pstate = block_plan, None
         if share_prefix and prefix_cache is None:
             plan = slots_run._prefix_plan(self, reqs, sched.slots, prefix_pool_tokens)
         elif share_prefix:                                        # the plan exactly as without a cache, then one lookup per request

@@ -22,6 +22,14 @@ Terms: request indices are arrival order = admission order.  An entry is named b
                 already moved to c) plus n must not exceed `pool_rows`.  Later creators only take readers away, so lives only shrink
                 and the bound holds for the final plan.  Without room c creates nothing and its would-be readers compute their own rows
                 (or read what an older entry offers): no request is refused or reordered.
+
+Block granularity (plan(..., block_rows=16), generate_many(kv_pool_tokens=, share_blocks=True)): on the paged K/V pool a
+shared prefix is not copied -- reader and creator NAME the same pool blocks -- so only whole blocks can be shared.  The plan is the plan
+above with every P_i and every entry length rounded DOWN to a multiple of block_rows (a length below one block counts as 0: the request
+then reads nothing and the entry, if nobody reads it, is dropped); source, creators, passes and lifetimes are otherwise unchanged, and
+P_i <= T_i - 1 still holds.  The rows between the last full block and what the exact plan reuses are recomputed.  vision_needed stays the
+exact plan's: a request whose image slot reaches behind its rounded P_i but whose exact plan needed no vision run takes the image
+features its source's creator used (image_from[i]: that creator; equal images by value), so those rows are computed from equal inputs.
 """
 from __future__ import annotations
 
@@ -53,6 +61,8 @@ class PrefixPlan:
     pool_rows: int
     min_shared_rows: int
     denied: List[int]                       # would-be creators that found the pool full
+    block_rows: int = 0                     # > 0: the plan at block granularity (P and entry lengths are multiples of it)
+    image_from: List[Optional[int]] = field(default_factory=list)     # block plan: the creator whose image features request i takes, or None
 
     @property
     def rows_reused(self) -> int:
@@ -88,10 +98,15 @@ def _match(ids: np.ndarray, lens: np.ndarray, c: int, J: np.ndarray, keys: Seque
 
 
 def plan(prompts: Sequence[Sequence[int]], image_keys: Sequence, img_token_id: Optional[int], slots: int, pool_rows: Optional[int] = None,
-         min_shared_rows: int = MIN_SHARED_ROWS) -> PrefixPlan:
+         min_shared_rows: int = MIN_SHARED_ROWS, block_rows: Optional[int] = None) -> PrefixPlan:
     """prompts[i]: the ids of request i (one per decoder position); image_keys[i]: None, or a value equal for equal images; slots: the
     decode batch (at most that many requests share a boundary); pool_rows: the pool bound in rows (None: DEFAULT_POOL_ENTRIES entries of
-    the longest prefix the queue would keep with an unbounded pool)."""
+    the longest prefix the queue would keep with an unbounded pool).  block_rows (None: today's plan): the plan at block granularity
+    (module header)."""
+    if block_rows is not None:
+        if isinstance(block_rows, bool) or not isinstance(block_rows, int) or block_rows < 1:
+            raise ValueError(f"prefix.plan: block_rows must be a positive integer (got {block_rows!r})")
+        return _to_blocks(plan(prompts, image_keys, img_token_id, slots, pool_rows, min_shared_rows), prompts, img_token_id, int(block_rows))
     if pool_rows is None:
         free = _plan(prompts, image_keys, img_token_id, slots, 1 << 40, min_shared_rows)
         free.pool_rows = DEFAULT_POOL_ENTRIES * max((e.rows for e in free.entries.values()), default=0)
@@ -163,6 +178,29 @@ def _plan(prompts, image_keys, img_token_id, slots, pool_rows, min_shared_rows) 
     source = [int(src[j]) if src[j] >= 0 else None for j in range(n)]
     vision = [image_keys[j] is not None and not (last_img[j] is not None and last_img[j] < P[j]) for j in range(n)]
     return PrefixPlan([int(t) for t in lens], P, source, vision, entries, int(slots), int(pool_rows), int(min_shared_rows), denied)
+
+
+def _to_blocks(pl: PrefixPlan, prompts, img_token_id: Optional[int], br: int) -> PrefixPlan:
+    """the exact plan `pl` at block granularity: P_i and entry lengths rounded down to multiples of br; who reads whom does not change"""
+    n = len(pl.T)
+    P = [p // br * br for p in pl.P]
+    source = [s if p > 0 else None for s, p in zip(pl.source, P)]
+    entries: Dict[int, Entry] = {}
+    for j in range(n):
+        if source[j] is not None:
+            c = source[j]
+            e = entries.setdefault(c, Entry(c, pl.entries[c].rows // br * br, j))
+            e.last_reader = j
+            e.readers.append(j)
+    image_from: List[Optional[int]] = [None] * n
+    vision = list(pl.vision_needed)
+    if img_token_id is not None:
+        for j in range(n):
+            if pl.source[j] is not None and pl.P[j] > 0 and not pl.vision_needed[j]:
+                last = max((k for k, t in enumerate(prompts[j]) if t == img_token_id), default=None)
+                if last is not None and last >= P[j]:             # the slot reaches behind the shared blocks: its rows need the image features
+                    image_from[j], vision[j] = (source[j], False) if source[j] is not None else (None, True)
+    return PrefixPlan(list(pl.T), P, source, vision, entries, pl.slots, pl.pool_rows, pl.min_shared_rows, list(pl.denied), br, image_from)
 
 
 def passes(pl: PrefixPlan, admitted: Sequence[int]) -> List[List[int]]:

@@ -62,22 +62,26 @@ class Pages:
 
 class PrefixShare:
     """share_prefix=True: the plan, this call's pool [rows, L, 2, H, d] with its free rows and the rows every creator holds, the rows P[i]
-    request i reuses and whether its image needs the vision stack (as the plan and a prefix cache's `pstate` combine), the counters"""
-    __slots__ = ("plan", "pool", "free", "rows", "P", "vis", "pstate", "reused", "computed", "vision", "passes", "calls")
+    request i reuses and whether its image needs the vision stack (as the plan and a prefix cache's `pstate` combine), the counters.
+    share_blocks=True (a plan at block granularity on the paged cache): the pool has no rows -- shared blocks are named, not copied -- and
+    feats[c] keeps the image features creator c's prompt was embedded with while its entry lives (plan.image_from)"""
+    __slots__ = ("plan", "pool", "free", "rows", "P", "vis", "pstate", "reused", "computed", "vision", "passes", "calls", "feats")
 
     def __init__(self, plan, pool: torch.Tensor, pstate: Optional[dict]):
         self.plan, self.pool, self.pstate, self.rows, self.free = plan, pool, pstate, {}, list(range(pool.shape[0] - 1, -1, -1))
         self.P, self.vis = (plan.P, plan.vision_needed) if pstate is None else (pstate["P"], pstate["vision"])   # (prefix_cache.combine)
         self.reused = self.computed = self.vision = self.passes = self.calls = 0
+        self.feats: Dict[int, torch.Tensor] = {}
 
 
-def _prefix_plan(model, reqs, slots: int, pool_rows: Optional[int], keys=None, prompts=None):
-    """the prefix plan of a queue (visualcla/prefix.py) from its ids and images (keys / prompts: _image_keys / _prompt_lists of the queue, when the caller needs them too)"""
+def _prefix_plan(model, reqs, slots: int, pool_rows: Optional[int], keys=None, prompts=None, block_rows: Optional[int] = None):
+    """the prefix plan of a queue (visualcla/prefix.py) from its ids and images (keys / prompts: _image_keys / _prompt_lists of the queue, when the caller needs them too);
+    block_rows: at block granularity (share_blocks=True)"""
     if pool_rows is not None and int(pool_rows) < 0:
         raise ValueError(f"prefix_pool_tokens must be >= 0 (got {pool_rows})")
     keys = _image_keys(model, reqs) if keys is None else keys
     prompts = _prompt_lists(reqs) if prompts is None else prompts
-    return prefix.plan(prompts, keys, model._special_ids()[2] if any(k is not None for k in keys) else None, slots, pool_rows)
+    return prefix.plan(prompts, keys, model._special_ids()[2] if any(k is not None for k in keys) else None, slots, pool_rows, block_rows=block_rows)
 
 
 def _prompt_lists(reqs):
@@ -219,7 +223,7 @@ class SlotsRun:
         self.samp = _lib.sample_args(uniforms=uni, history=hist, **samp_kw) if samp_kw is not None else None
         self.count_h, self.share = [0] * B, None
         if plan is not None:                                    # the prefix pool of this call: [rows, L, 2, H, d], 2 L H d elements per row
-            n_rows = min(plan.pool_rows, plan.peak_pool_rows)
+            n_rows = min(plan.pool_rows, plan.peak_pool_rows) if self.pages is None else 0      # paged: blocks are shared by reference
             self.share = PrefixShare(plan, torch.empty(n_rows, t["num_hidden_layers"], 2, H, d, dtype=model._dtype, device=self.dev), pstate)
 
     def run(self):
@@ -420,8 +424,12 @@ class SlotsRun:
         """share_prefix=True: the requests admitted at one boundary, every one at position 0 of its slot.  In the passes of prefix.passes: copy
         the rows [0, P_i) each request reuses from the pool into its slot (one indexed copy per pass), run the vision stack over the images
         that are needed, then ONE vcla_llama_extend_rows over the rows [P_i, T_i) of all of them, written straight into the slots; the
-        creators of the pass then leave their leading rows in the pool (one indexed copy)."""
+        creators of the pass then leave their leading rows in the pool (one indexed copy).
+        share_blocks=True (self.pages): nothing is copied in either direction.  The scheduler has put the source entry's blocks at the head of
+        every reader's table row; the rows of a pass are validated (no block with several holders is written) and uploaded, and the pass
+        runs on the pool through vcla_llama_extend_rows_paged (extend_paged)."""
         m, dev, reqs, kv, sh, B = self.m, self.dev, self.reqs, self.kv, self.share, self.sched.slots
+        paged = self.pages is not None
         plan, pool, P, pstate = sh.plan, sh.pool, sh.P, sh.pstate
         cached = pstate["from_cache"] if pstate is not None else [False] * len(P)
         slot_of = dict(zip(g.requests, g.slots))
@@ -434,30 +442,41 @@ class SlotsRun:
             si = torch.tensor([b for b, _, rows in pairs for _ in rows], device=dev)
             ri = torch.tensor([r0 + k for _, r0, rows in pairs for k in range(len(rows))], device=dev)
             return pi, si, ri
-        for members in prefix.passes(plan, g.requests):
+        all_passes = prefix.passes(plan, g.requests)
+        for k_pass, members in enumerate(all_passes):
             sh.passes += 1
-            reads = [(slot_of[i], 0, sh.rows[plan.source[i]][:P[i]]) for i in members if P[i] > 0 and not cached[i]]
+            if paged:
+                self.fill_shared_pages(members, [i for later in all_passes[k_pass + 1:] for i in later], slot_of)
+            reads = [(slot_of[i], 0, sh.rows[plan.source[i]][:P[i]]) for i in members if P[i] > 0 and not cached[i]] if not paged else []
             if reads:
                 pi, si, ri = index(reads)
                 kv[:, :, si, :, ri] = pool[pi]
             if pstate is not None:                              # the rows the prefix cache holds: its blocks into the slots, one launch
                 _lib.kv_blocks_copy(kv, pstate["cache"].pool, pstate["cache"].read_entries(pstate, members, slot_of), to_pool=False)
             # ---- embeddings of whole prompts, by classes of equal (length, image, vision needed): one check and one splice per class
+            # (paged: a request whose slot reaches behind its shared blocks but needs no vision run takes its creator's features, class value 2)
             classes: Dict[tuple, List[int]] = {}
             for i in members:
-                classes.setdefault((int(reqs[i]["ids"].numel()), reqs[i]["px"] is not None, sh.vis[i]), []).append(i)
+                vis = 1 if sh.vis[i] else (2 if paged and plan.image_from[i] is not None else 0)
+                classes.setdefault((int(reqs[i]["ids"].numel()), reqs[i]["px"] is not None, vis), []).append(i)
             emb_of: Dict[int, torch.Tensor] = {}
             for (T, has_px, vis), cls in classes.items():
                 ids = torch.stack([reqs[i]["ids"] for i in cls])
                 img_pos, _ = m._check_request(ids, None, Q if has_px else 0, for_generate=True)
-                img = m.embed_images(torch.stack([reqs[i]["px"] for i in cls])) if vis else None
-                sh.vision += len(cls) if vis else 0
+                img = m.embed_images(torch.stack([reqs[i]["px"] for i in cls])) if vis == 1 else None
+                if vis == 2:
+                    img = torch.stack([sh.feats[plan.image_from[i]] for i in cls])
+                sh.vision += len(cls) if vis == 1 else 0
                 embeds, _ = m._embed(ids, img, img_pos if vis else None)
                 for j, i in enumerate(cls):
                     emb_of[i] = embeds[j, P[i]:]
+                    if paged and img is not None and i in plan.entries:
+                        sh.feats[i] = img[j].clone()
             for call in cut_calls(rows_of, members, RAGGED_MAX_ROWS, _lib.EXTEND_MAX_ROWS):
                 table = [(slot_of[i], P[i], rows_of[i]) for i in call]
-                logits = m._extend_rows(torch.cat([emb_of[i] for i in call]), table, kv, ws_for=(min(RAGGED_MAX_ROWS, B * max(plan.T)), B))
+                ws_for = (min(RAGGED_MAX_ROWS, B * max(plan.T)), B)
+                logits = self.extend_paged(torch.cat([emb_of[i] for i in call]), call, table, ws_for) if paged else \
+                    m._extend_rows(torch.cat([emb_of[i] for i in call]), table, kv, ws_for=ws_for)
                 sh.calls += 1
                 if m._inflight_logits_tap is not None:
                     m._inflight_logits_tap.append((list(call), logits.detach().clone()))
@@ -469,7 +488,7 @@ class SlotsRun:
             # ---- the creators of this pass leave their rows in the pool; entries whose last reader this pass held are released
             made = []
             for i in members:
-                e = plan.entries.get(i)
+                e = plan.entries.get(i) if not paged else None
                 if e is not None:
                     sh.rows[i] = [sh.free.pop() for _ in range(e.rows)]
                     made.append((slot_of[i], 0, sh.rows[i]))
@@ -479,10 +498,47 @@ class SlotsRun:
             for i in members:
                 s_ = plan.source[i]
                 if s_ is not None and plan.entries[s_].last_reader == i:
-                    sh.free.extend(sh.rows.pop(s_))
+                    if paged:
+                        sh.feats.pop(s_, None)
+                    else:
+                        sh.free.extend(sh.rows.pop(s_))
             if pstate is not None:                              # the members' full blocks that the prefix cache lacks: out of the slots, one launch
                 _lib.kv_blocks_copy(kv, pstate["cache"].pool, pstate["cache"].insert_entries(pstate, members, slot_of), to_pool=True)
         self.start_slots(g.requests, g.slots, [first_of[i] for i in g.requests], plan.T)      # every slot decodes from its own T
+
+    def fill_shared_pages(self, members, pending, slot_of) -> None:
+        """share_blocks: the table rows of the requests of one pass, as the scheduler assembled them (shared blocks first), validated on
+        the host before the upload: entries in range, enough blocks, and a block named by several rows only at one logical index, listed as
+        shared by each and below each one's P_i / 16 -- so nothing with more than one holder is ever written"""
+        pg = self.pages
+        rows, needs, shared, owned = self.sched.page_rows(members, pending)
+        t = _lib.kv_page_rows(rows, needs, pg.n_blocks, pg.table.shape[1], owned, shared=shared)
+        pg.table[torch.tensor([slot_of[i] for i in members], device=self.dev)] = t.to(self.dev)
+
+    def extend_paged(self, embeds: torch.Tensor, call, table, ws_for) -> torch.Tensor:
+        """one ragged pass on the pool -> the last-row logits.  The kernel route (bf16, head dim 64 / 128, blocks of at most 256 rows) is
+        vcla_llama_extend_rows_paged.  Otherwise -- the parity route -- the rows [0, P_i) are gathered from the blocks into a private
+        contiguous cache [L, 2, n, H, max T, d] (allocated per call), vcla_llama_extend_rows runs there, and the rows [P_i, T_i) are copied
+        into the slots' blocks as fill_pages copies"""
+        m, sched, kv, R = self.m, self.sched, self.kv, _lib.KV_BLOCK_ROWS
+        L, _, H, _, d = kv.shape
+        if m._dtype == torch.bfloat16 and d in (64, 128) and all(r <= _lib.EXTEND_MAX_ROWS for _, _, r in table):
+            return m._extend_rows(embeds, table, kv, ws_for=ws_for, pages=self.pages, ctx_max=sched.ctx_max)
+        Tm = max(p + r for _, p, r in table)
+        own = torch.zeros(L, 2, len(call), H, Tm, d, dtype=kv.dtype, device=self.dev)
+
+        def rows_index(lo_hi):
+            return torch.tensor([sched.blocks[i][r // R] * R + r % R for i, (lo, hi) in zip(call, lo_hi) for r in range(lo, hi)], device=self.dev)
+        lead = [(k, p) for k, (_, p, _) in enumerate(table) if p > 0]
+        if lead:
+            si = torch.tensor([k for k, p in lead for _ in range(p)], device=self.dev)
+            ri = torch.tensor([r for _, p in lead for r in range(p)], device=self.dev)
+            own[:, :, si, :, ri] = kv[:, :, :, rows_index([(0, p) for _, p, _ in table])].permute(3, 0, 1, 2, 4)
+        logits = m._extend_rows(embeds, [(k, p, r) for k, (_, p, r) in enumerate(table)], own, ws_for=ws_for)
+        si = torch.tensor([k for k, (_, p, r) in enumerate(table) for _ in range(r)], device=self.dev)
+        ri = torch.tensor([x for _, p, r in table for x in range(p, p + r)], device=self.dev)
+        kv[:, :, :, rows_index([(p, p + r) for _, p, r in table])] = own[:, :, si, :, ri].permute(1, 2, 3, 0, 4)
+        return logits
 
     def decode_chunk(self, n: int) -> None:
         """n steps of every live slot, one call; the per-slot tables, the logprob block, the constraints and the stop table are null where the feature is off"""
