@@ -58,6 +58,8 @@ struct EgMisc {                            // LDS words shared by the four waves
 static_assert(sizeof(EgMisc) <= 4096, "misc region");
 
 __device__ __forceinline__ unsigned eg_ld(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+// a flag word as the consumers read it: every lane loads the same word, and readfirstlane lets hipcc branch on it with SCALAR branches
+__device__ __forceinline__ unsigned eg_ldu(const unsigned* p) { return __builtin_amdgcn_readfirstlane(eg_ld(p)); }
 __device__ __forceinline__ void eg_st(unsigned* p, unsigned v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 __device__ __forceinline__ void eg_release() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local"); }
 __device__ __forceinline__ void eg_acquire() { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local"); }
@@ -74,14 +76,24 @@ __device__ __forceinline__ void eg_fail(EgMisc* m, unsigned* state, unsigned cod
     eg_st(&m->fail, code);
     if ((threadIdx.x & 63) == 0) atomicCAS(state + 1, 0u, code | (blockIdx.x << 16));
 }
-// wait until *p >= need (LDS word written by another wave of this workgroup)
+// wait until *p >= need (LDS word written by another wave of this workgroup).  UNI: the consumers' form (eg_ldu)
+template <bool UNI = false>
 __device__ __forceinline__ bool eg_wait_ge(const unsigned* p, unsigned need, EgMisc* m, unsigned* state, unsigned code) {
     for (unsigned it = 0;; ++it) {
-        if (eg_ld(p) >= need) return true;
-        if ((it & 63) == 63 && eg_ld(&m->fail)) return false;
+        if ((UNI ? eg_ldu(p) : eg_ld(p)) >= need) return true;
+        if ((it & 63) == 63 && (UNI ? eg_ldu(&m->fail) : eg_ld(&m->fail))) return false;
         if (it > EG_SPIN_LDS) { eg_fail(m, state, code); return false; }
         __builtin_amdgcn_s_sleep(1);
     }
+}
+// A CONSUMER wave that gives up ends right here.  (It used to `return false` up through every caller to the end of the kernel.  That is the same
+// thing at run time, but ~50 exits out of the layer loop: hipcc joins them through chains of flag blocks, on whose paths every register array
+// -- the preloaded slots above all -- looks defined in one phase and used in another, and so stays allocated across ALL phases.  Those paths cost
+// ~300 registers.  A wave that ends in place leaves the loop with one exit.)  The loader does not use this: it breaks out and writes its totals.
+__device__ __forceinline__ void eg_leave() { asm volatile("s_endpgm" ::: "memory"); }
+// the consumers' wait: back only when *p >= need
+__device__ __forceinline__ void eg_await(const unsigned* p, unsigned need, EgMisc* m, unsigned* state, unsigned code) {
+    if (!eg_wait_ge<true>(p, need, m, state, code)) eg_leave();
 }
 
 template <int CTRL> __device__ __forceinline__ float eg_dpp(float v) {
@@ -166,7 +178,7 @@ __device__ __forceinline__ void eg_stamp(const EgCtx& c, int layer, int k) {
 
 // ---- sweep NCH x 1024 granules starting at mb (ONE wave): v[k] = data of granule lane + 64 k
 template <int NCH>
-__device__ __forceinline__ bool eg_sweep(EgCtx& c, const unsigned long long* mb, unsigned epoch, unsigned (&v)[NCH * 16], int n_gran, unsigned code) {
+__device__ __forceinline__ void eg_sweep(EgCtx& c, const unsigned long long* mb, unsigned epoch, unsigned (&v)[NCH * 16], int n_gran, unsigned code) {
     // all NCH x 16 loads of the lane are in flight together (a pass is latency-bound: ~1 us for 16 loads, not much more for 32)
     for (unsigned it = 0;; ++it) {
         bool good = true;
@@ -179,15 +191,14 @@ __device__ __forceinline__ bool eg_sweep(EgCtx& c, const unsigned long long* mb,
             good = good && (unsigned)(x >> 32) == epoch;
         }
         if (__all(good)) break;
-        if ((it & 15) == 15 && eg_ld(&c.m->fail)) return false;
-        if (it > EG_SPIN_GLB) { eg_fail(c.m, c.state, code); return false; }
+        if ((it & 15) == 15 && eg_ldu(&c.m->fail)) eg_leave();
+        if (it > EG_SPIN_GLB) { eg_fail(c.m, c.state, code); eg_leave(); }
         __builtin_amdgcn_s_sleep(8);
     }
-    return true;
 }
 
 // ---- leader: stage RMSNorm(x) * gamma (bf16) as the next operator's input.  x = the 2048-granule mailbox `mb`, or x_in (plain memory, layer 0)
-__device__ __forceinline__ bool eg_stage_norm(EgCtx& c, const unsigned long long* mb, unsigned epoch, const float* gamma, bool from_mem) {
+__device__ __forceinline__ void eg_stage_norm(EgCtx& c, const unsigned long long* mb, unsigned epoch, const float* gamma, bool from_mem) {
     float2 gm[32];
 #pragma unroll
     for (int k = 0; k < 32; ++k) gm[k] = *reinterpret_cast<const float2*>(gamma + 2 * (c.lane + 64 * k));
@@ -197,8 +208,7 @@ __device__ __forceinline__ bool eg_stage_norm(EgCtx& c, const unsigned long long
 #pragma unroll
         for (int k = 0; k < 32; ++k) v[k] = xi[c.lane + 64 * k];
     } else {
-        const bool good = eg_sweep<2>(c, mb, epoch, v, 2048, 0x11);
-        if (!good) return false;
+        eg_sweep<2>(c, mb, epoch, v, 2048, 0x11);
     }
     float ss = 0.f;
 #pragma unroll
@@ -209,11 +219,10 @@ __device__ __forceinline__ bool eg_stage_norm(EgCtx& c, const unsigned long long
 #pragma unroll
     for (int k = 0; k < 32; ++k) xo[c.lane + 64 * k] = pack_bf2(eg_lo(v[k]) * rstd * gm[k].x, eg_hi(v[k]) * rstd * gm[k].y);
     if (from_mem && c.lane < 16) c.m->resid0[c.lane] = bf2f(c.a->x_in[16 * c.cu + c.lane]);
-    return true;
 }
 // ---- a landed slot: LDS -> registers (16 x 16 bytes per lane), ring position released at once
-__device__ __forceinline__ bool eg_fetch(EgCtx& c, int g, u32x4_t (&wv)[16], unsigned code) {
-    if (!eg_wait_ge(&c.m->filled, (unsigned)g + 1, c.m, c.state, code)) return false;
+__device__ __forceinline__ void eg_fetch(EgCtx& c, int g, u32x4_t (&wv)[16], unsigned code) {
+    eg_await(&c.m->filled, (unsigned)g + 1, c.m, c.state, code);
     eg_acquire();
     const int rp = g % EG_NRING;
     const unsigned char* base = c.ring + rp * EG_SLOT + c.lane * 16;
@@ -221,7 +230,6 @@ __device__ __forceinline__ bool eg_fetch(EgCtx& c, int g, u32x4_t (&wv)[16], uns
     for (int p = 0; p < 16; ++p) wv[p] = *reinterpret_cast<const u32x4_t*>(base + p * 1024);
     eg_release();                                  // (waits for the reads above)
     eg_st(&c.m->freed[rp], (unsigned)g + 1);
-    return true;
 }
 // ---- two rows of 4096 weights (one slot of a row-major operator) against the x registers -> two wave-uniform sums
 __device__ __forceinline__ void eg_rows2(const u32x4_t (&wv)[16], const u32x4_t (&xr)[8], float& t0, float& t1) {
@@ -238,16 +246,21 @@ enum { EG_OP_QKV = 0, EG_OP_O = 1, EG_OP_GU = 2, EG_OP_LM = 3, EG_OP_DN = 4 };
 // layer last 4 - 12 us (attention + its all-gather: 11), and whenever the ring is full the weight stream stops.  A consumer wave owns a SIMD (512
 // registers), so consumers 1 and 2 take the FIRST 2 x NP slots of every operator (alternating) into registers as they land -- the leader sweeps the
 // mailbox then, and a slot it owned would block the ring behind it -- and the three share the rest round-robin.
+// The counts are what the window "qkv done -> gate/up starts" asks for (~18 us with only o_proj's 8 slots consumed inside it), not what the registers
+// allow: with the failure exits out of the layer loop (eg_leave) the kernel needs 322 registers at 1 / 1 / 2 / 1 and 386 of 512 at 2 / 2 / 4 / 2
+// (profiles/engine_preload_depth.txt).
 #ifndef EG_PRE
-#define EG_PRE 1            // qkv, down_proj, lm_head (more than 1 / 2 / 1 sends hipcc into scratch: ~330 registers of phase state stay live whatever the count)
+#define EG_PRE 2            // qkv, down_proj, lm_head: the x edge (the loader may reach slot 2 * 2 + EG_NRING = 13 while x is gathered); down_proj needs 3 * EG_PRE <= gpc
 #endif
 #ifndef EG_PRE_GU
-#define EG_PRE_GU 2         // gate/up: whole pairs (the two activations of one granule)
+#define EG_PRE_GU 4         // gate/up: whole pairs (the two activations of one granule); the loader may reach slot 32 + 2 * 4 + EG_NRING = 49 before gate/up starts
 #endif
 #ifndef EG_PRE_O
-#define EG_PRE_O 1          // o_proj: live ACROSS the attention code
+#define EG_PRE_O 2          // o_proj: live ACROSS the attention code -- 6 of its 8 slots are in registers before the attention output exists (limit 24 + 3 * 2 + EG_NRING = 39)
 #endif
 #define EG_PRE_MAX 4
+static_assert(3 * EG_PRE_O <= EG_S_O, "o_proj holds the unconditional register preloads");
+static_assert(3 * EG_PRE <= 2 * EG_PRE_MAX, "down_proj (gpc >= 2 * EG_PRE_MAX, vcla_engine_geometry) holds its 3 * EG_PRE preloaded slots");
 template <int OP> struct EgUnit {          // slots per unit (gate/up: the pair of one granule), preloaded slots / units per wave, first round-robin unit
     static constexpr int US = OP == EG_OP_GU ? 2 : 1, NP = OP == EG_OP_O ? EG_PRE_O : OP == EG_OP_GU ? EG_PRE_GU : EG_PRE, PU = NP / US, F = 2 * PU;
     static_assert(NP % US == 0 && NP <= EG_PRE_MAX && NP >= 1, "preload counts");
@@ -255,26 +268,26 @@ template <int OP> struct EgUnit {          // slots per unit (gate/up: the pair 
 
 // consumers 1 / 2: preload units (w - 1) + 2 i, i < PU.  Unconditional (the geometry guarantees every operator has at least 2 * EG_PRE_MAX slots): a
 // conditionally defined register array becomes a loop-carried value of the layer loop and is kept live across every phase.
-template <int OP, int NP>
-__device__ __forceinline__ bool eg_preload(EgCtx& c, int g0, u32x4_t (&pre)[NP][16]) {
+// (I0, I1: the part pre[I0 .. I1) of them -- o_proj takes its second slot per wave INSIDE the attention, see eg_consumer)
+template <int OP, int NP, int I0 = 0, int I1 = NP>
+__device__ __forceinline__ void eg_preload(EgCtx& c, int g0, u32x4_t (&pre)[NP][16]) {
     using U = EgUnit<OP>;
-    static_assert(NP == U::PU * U::US, "preload registers");
+    static_assert(NP == U::PU * U::US && 0 <= I0 && I0 <= I1 && I1 <= NP, "preload registers");
 #pragma unroll
-    for (int i = 0; i < NP; ++i) {
+    for (int i = I0; i < I1; ++i) {
         // K-major operators (no gather phase: the leader is a consumer like the others): slots w, w + 3, ...; row-major ones: consumers 1 / 2 alternate
         const int slot = (OP == EG_OP_O || OP == EG_OP_DN) ? c.w + 3 * i : ((c.w - 1) + 2 * (i / U::US)) * U::US + (i % U::US);
-        if (!eg_fetch(c, g0 + slot, pre[i], 0x21)) return false;
+        eg_fetch(c, g0 + slot, pre[i], 0x21);
     }
-    return true;
 }
 
 // ---- a row-major operator (K = 4096) over nslots slots starting at global slot g0.  LEADER (consumer 0) has no preloaded slots (`pre` unused)
 template <int OP, bool LEADER>
-__device__ __forceinline__ bool eg_run_rows(EgCtx& c, int g0, int nslots, int layer, unsigned seq, const u32x4_t (*pre)[16]) {
+__device__ __forceinline__ void eg_run_rows(EgCtx& c, int g0, int nslots, int layer, unsigned seq, const u32x4_t (*pre)[16]) {
     using U = EgUnit<OP>;
     const vcla_engine_args& a = *c.a;
     const int gpc = (a.g.upc + 1) >> 1;
-    if (!eg_wait_ge(&c.m->xin_ready, seq, c.m, c.state, 0x22)) return false;
+    eg_await(&c.m->xin_ready, seq, c.m, c.state, 0x22);
     eg_acquire();
     u32x4_t xr[8];
 #pragma unroll
@@ -319,7 +332,7 @@ __device__ __forceinline__ bool eg_run_rows(EgCtx& c, int g0, int nslots, int la
             if (slot < nslots) {
                 u32x4_t wv[16];
                 float t0, t1;
-                if (!eg_fetch(c, g0 + slot, wv, 0x21)) return false;
+                eg_fetch(c, g0 + slot, wv, 0x21);
                 eg_rows2(wv, xr, t0, t1);
                 finish(slot, t0, t1);
             }
@@ -330,12 +343,11 @@ __device__ __forceinline__ bool eg_run_rows(EgCtx& c, int g0, int nslots, int la
     }
     eg_release();
     eg_st(&c.m->cons_done[c.w], seq);
-    return true;
 }
 
 // ---- the greedy tail (args.tail_ids_out != NULL): every CU's leader publishes the maximum of its share of the logits, CU 0 picks the winner and does the
 // step's bookkeeping -- what vcla_argmax + post_select_kernel did in two more launches (same tie rule: the lowest index among equal maxima; NaN never wins)
-__device__ __forceinline__ bool eg_greedy_tail(EgCtx& c, int L) {
+__device__ __forceinline__ void eg_greedy_tail(EgCtx& c, int L) {
     const vcla_engine_args& a = *c.a;
     EgMisc* m = c.m;
     float best = m->amax_v[0];
@@ -352,7 +364,7 @@ __device__ __forceinline__ bool eg_greedy_tail(EgCtx& c, int L) {
         eg_publish(mb, c.cu, ep, __float_as_uint(best));
         eg_publish(mb, EG_NCU + c.cu, ep, (unsigned)bi);
     }
-    if (c.cu != 0) return true;
+    if (c.cu != 0) return;
     float v[4];
     int ix[4];
     for (unsigned it = 0;; ++it) {
@@ -365,8 +377,8 @@ __device__ __forceinline__ bool eg_greedy_tail(EgCtx& c, int L) {
             good = good && (unsigned)(xv >> 32) == ep && (unsigned)(xi >> 32) == ep;
         }
         if (__all(good)) break;
-        if ((it & 15) == 15 && eg_ld(&m->fail)) return false;
-        if (it > EG_SPIN_GLB) { eg_fail(m, c.state, 0x51); return false; }
+        if ((it & 15) == 15 && eg_ldu(&m->fail)) eg_leave();
+        if (it > EG_SPIN_GLB) { eg_fail(m, c.state, 0x51); eg_leave(); }
         __builtin_amdgcn_s_sleep(4);
     }
     best = v[0]; bi = ix[0];
@@ -391,7 +403,6 @@ __device__ __forceinline__ bool eg_greedy_tail(EgCtx& c, int L) {
     u32x4_t* dst = reinterpret_cast<u32x4_t*>(a.tail_x);
 #pragma unroll
     for (int k = 0; k < 8; ++k) dst[c.lane + 64 * k] = src[c.lane + 64 * k];
-    return true;
 }
 
 // ---- 256 granules [256 j, 256 j + 256) of a mailbox = the 512 input values slot j of a K-major operator multiplies: lane l takes granules 4 l .. 4 l + 3,
@@ -402,19 +413,18 @@ __device__ __forceinline__ void eg_slice_issue(const EgCtx& c, const unsigned lo
 #pragma unroll
     for (int q = 0; q < 4; ++q) s.g[q] = eg_peek(mb, 256 * j + 4 * c.lane + q);
 }
-__device__ __forceinline__ bool eg_slice_take(EgCtx& c, const unsigned long long* mb, int j, unsigned epoch, EgSlice& s, u32x4_t& xk, unsigned code) {
+__device__ __forceinline__ void eg_slice_take(EgCtx& c, const unsigned long long* mb, int j, unsigned epoch, EgSlice& s, u32x4_t& xk, unsigned code) {
     for (unsigned it = 0;; ++it) {
         bool good = true;
 #pragma unroll
         for (int q = 0; q < 4; ++q) good = good && (unsigned)(s.g[q] >> 32) == epoch;
         if (__all(good)) break;
-        if ((it & 15) == 15 && eg_ld(&c.m->fail)) return false;
-        if (it > EG_SPIN_GLB) { eg_fail(c.m, c.state, code); return false; }
+        if ((it & 15) == 15 && eg_ldu(&c.m->fail)) eg_leave();
+        if (it > EG_SPIN_GLB) { eg_fail(c.m, c.state, code); eg_leave(); }
         __builtin_amdgcn_s_sleep(2);
         eg_slice_issue(c, mb, j, s);
     }
     xk = u32x4_t{(unsigned)s.g[0], (unsigned)s.g[1], (unsigned)s.g[2], (unsigned)s.g[3]};
-    return true;
 }
 
 // ---- a K-major operator (o_proj: OP = EG_OP_O, down_proj: EG_OP_DN): slot j = the CU's 16 output rows x 512 inputs.  No gather phase: every wave reads
@@ -422,7 +432,7 @@ __device__ __forceinline__ bool eg_slice_take(EgCtx& c, const unsigned long long
 // first granules are published.  The leader adds the three consumers' partial sums and the residual, rounds to bf16 and publishes the 16 outputs
 // (o_proj: x1 = x + o_proj(...); down_proj: the next layer's x).
 template <int OP, bool LEADER>
-__device__ __forceinline__ bool eg_run_kmajor(EgCtx& c, int g0, int nslots, int layer, unsigned seq, const unsigned long long* mb, unsigned epoch,
+__device__ __forceinline__ void eg_run_kmajor(EgCtx& c, int g0, int nslots, int layer, unsigned seq, const unsigned long long* mb, unsigned epoch,
                                               const u32x4_t (*pre)[16]) {
     constexpr int NP = EgUnit<OP>::NP;
     float acc[16];
@@ -439,7 +449,7 @@ __device__ __forceinline__ bool eg_run_kmajor(EgCtx& c, int g0, int nslots, int 
 #pragma unroll
     for (int i = 0; i < NP; ++i, ++t) {
         u32x4_t xk;
-        if (!eg_slice_take(c, mb, slot_of(t), epoch, q0, xk, 0x27)) return false;
+        eg_slice_take(c, mb, slot_of(t), epoch, q0, xk, 0x27);
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = eg_dot8s(pre[i][r], xk, acc[r]);
         q0 = q1; q1 = q2;
@@ -447,9 +457,9 @@ __device__ __forceinline__ bool eg_run_kmajor(EgCtx& c, int g0, int nslots, int 
     }
     for (; slot_of(t) < nslots; ++t) {
         u32x4_t wv[16];
-        if (!eg_fetch(c, g0 + slot_of(t), wv, 0x24)) return false;
+        eg_fetch(c, g0 + slot_of(t), wv, 0x24);
         u32x4_t xk;
-        if (!eg_slice_take(c, mb, slot_of(t), epoch, q0, xk, 0x28)) return false;
+        eg_slice_take(c, mb, slot_of(t), epoch, q0, xk, 0x28);
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = eg_dot8s(wv[r], xk, acc[r]);
         q0 = q1; q1 = q2;
@@ -462,7 +472,8 @@ __device__ __forceinline__ bool eg_run_kmajor(EgCtx& c, int g0, int nslots, int 
     eg_release();
     eg_st(&c.m->cons_done[c.w], seq);
     if constexpr (LEADER) {
-        if (!eg_wait_ge(&c.m->cons_done[1], seq, c.m, c.state, 0x25) || !eg_wait_ge(&c.m->cons_done[2], seq, c.m, c.state, 0x26)) return false;
+        eg_await(&c.m->cons_done[1], seq, c.m, c.state, 0x25);
+        eg_await(&c.m->cons_done[2], seq, c.m, c.state, 0x26);
         eg_acquire();
         const int l = c.lane & 15;
         const float res = OP == EG_OP_O ? c.m->resid0[l] : c.m->resid1[l];
@@ -475,17 +486,19 @@ __device__ __forceinline__ bool eg_run_kmajor(EgCtx& c, int g0, int nslots, int 
             else eg_publish(eg_mb(c, layer + 1, EG_MB_X), 8 * c.cu + (c.lane >> 1), eg_epoch(c, layer + 1, 0), pack_bf2(vr, nb));
         }
     }
-    return true;
 }
 
 // ---- attention of one head on this CU's three consumers (RoPE + cache append + single-pass online softmax over the cache; the arithmetic of
 // attn_decode_flash_kernel<128, NW, MASK>, attention_decode.hip, with NW = 3).  U keys per lane group and batch, two batches in flight.
-// (8 keys per batch = 192 keys requested before q exists; the MASK instantiation is 8 registers short for that with o_proj slots held across this code: 6)
+// (8 keys per batch = 192 keys requested before q exists; 6 in the MASK and SPLITK instantiations, which were short of registers when this was written.  The
+// batch size decides which keys share a rescaling of the running sums, so it stays what it is: outputs are bit-identical from one build to the next.)
 // SPLIT (long contexts, args.split_min): the head's cached keys are dealt over all 8 CUs of its group (CU 8 h + s takes the key streams 12 s .. 12 s + 11 of
 // 96); the 7 helpers (OWNER = false) publish their unnormalised (o[128], m, l) as fp32 granules and the owner merges them with its own share and the new
 // token.  One more hand-off on the layer's critical path (~2 - 3 us), 7/8 of the cache walk off it (~1 us per 100 keys on ONE CU).
-template <bool MASK, bool LEADER, bool OWNER, bool split, bool SPLITK = split>
-__device__ __forceinline__ bool eg_attention(EgCtx& c, int layer) {
+// `mid()` runs once per wave between the request for the first key batches and the first use of q: the leader after it has staged q (the ~2 us it waits
+// for the q / k / v granules are the layer's critical path: nothing goes in front of that wait), the other waves before they wait for the leader.
+template <bool MASK, bool LEADER, bool OWNER, bool split, bool SPLITK = split, typename MID>
+__device__ __forceinline__ void eg_attention(EgCtx& c, int layer, MID&& mid) {
     constexpr int D = EG_HD, LPK = 16, KPW = 4, U = (MASK || SPLITK) ? 6 : 8;       // (8 keys per batch only where the registers allow: the short-context kernel without a mask)
     constexpr int KPB = split ? 96 : 12;                             // key streams of the head: 12 per CU
     static_assert(OWNER || split, "a helper exists only when the walk is split");
@@ -533,8 +546,8 @@ __device__ __forceinline__ bool eg_attention(EgCtx& c, int layer) {
             qd = (unsigned)xq; kd = (unsigned)xk; vd = (unsigned)xv;
             const bool good = (unsigned)(xq >> 32) == ep && (unsigned)(xk >> 32) == ep && (unsigned)(xv >> 32) == ep;
             if (__all(good)) break;
-            if ((it & 15) == 15 && eg_ld(&m->fail)) return false;
-            if (it > EG_SPIN_GLB) { eg_fail(m, c.state, 0x31); return false; }
+            if ((it & 15) == 15 && eg_ldu(&m->fail)) eg_leave();
+            if (it > EG_SPIN_GLB) { eg_fail(m, c.state, 0x31); eg_leave(); }
             __builtin_amdgcn_s_sleep(2);
         }
         eg_stamp(c, layer, 10);
@@ -557,8 +570,10 @@ __device__ __forceinline__ bool eg_attention(EgCtx& c, int layer) {
         eg_release();
         eg_st(&m->attn_ready, seq);
         eg_stamp(c, layer, 11);
+        mid();
     } else {
-        if (!eg_wait_ge(&m->attn_ready, seq, m, c.state, 0x32)) return false;
+        mid();
+        eg_await(&m->attn_ready, seq, m, c.state, 0x32);
     }
     eg_acquire();
     const u32x4_t qv = *reinterpret_cast<const u32x4_t*>(m->qpk + cch * 4);
@@ -641,7 +656,8 @@ __device__ __forceinline__ bool eg_attention(EgCtx& c, int layer) {
     eg_st(&m->attn_done[c.w], seq);
     if constexpr (LEADER) {
         eg_stamp(c, layer, 12);
-        if (!eg_wait_ge(&m->attn_done[1], seq, m, c.state, 0x33) || !eg_wait_ge(&m->attn_done[2], seq, m, c.state, 0x34)) return false;
+        eg_await(&m->attn_done[1], seq, m, c.state, 0x33);
+        eg_await(&m->attn_done[2], seq, m, c.state, 0x34);
         eg_acquire();
         float mf = fmaxf(fmaxf(m->part[0][D], m->part[1][D]), m->part[2][D]);      // (every lane: the 3 waves of this CU)
         float lf = 0.f, o8[8];
@@ -670,7 +686,7 @@ __device__ __forceinline__ bool eg_attention(EgCtx& c, int layer) {
                     for (int e = 0; e < 8; ++e) eg_publish(mine, lane * 8 + e, epp, __float_as_uint(o8[e]));
                     if (lane == 0) { eg_publish(mine, D, epp, __float_as_uint(mf)); eg_publish(mine, D + 1, epp, __float_as_uint(lf)); }
                 }
-                return true;
+                return;
             } else {
                 // the owner: lane group g merges the shares of CUs g and g + 4 of the head's group (its own: the registers above), then the groups meet
                 const int own = c.cu & 7, g = lane >> 4, l16 = lane & 15;
@@ -699,8 +715,8 @@ __device__ __forceinline__ bool eg_attention(EgCtx& c, int layer) {
                             }
                         }
                         if (__all(good)) break;
-                        if ((it & 15) == 15 && eg_ld(&m->fail)) return false;
-                        if (it > EG_SPIN_GLB) { eg_fail(m, c.state, 0x35); return false; }
+                        if ((it & 15) == 15 && eg_ldu(&m->fail)) eg_leave();
+                        if (it > EG_SPIN_GLB) { eg_fail(m, c.state, 0x35); eg_leave(); }
                         __builtin_amdgcn_s_sleep(2);
                     }
                     const float mn_ = fmaxf(rm, pm);
@@ -736,7 +752,6 @@ __device__ __forceinline__ bool eg_attention(EgCtx& c, int layer) {
             }
         }
     }
-    return true;
 }
 
 // One consumer wave over the whole step.  LEADER = consumer 0: sweeps the mailboxes, stages every operator's input vector, finishes down_proj,
@@ -753,8 +768,9 @@ __device__ __forceinline__ void eg_consumer(EgCtx& c) {
     // register allocation of the WHOLE kernel hinges on it: without the redundant test the split-capable kernels spill 16 - 25 registers to scratch)
     const bool split = SPLITK && a.split_min > 0 && c.pos >= a.split_min;
     // the leader may overwrite xin only when the other consumers have finished the operator that reads it
-    auto others_done = [&](unsigned seq) -> bool {
-        return eg_wait_ge(&m->cons_done[1], seq, m, c.state, 0x41) && eg_wait_ge(&m->cons_done[2], seq, m, c.state, 0x42);
+    auto others_done = [&](unsigned seq) {
+        eg_await(&m->cons_done[1], seq, m, c.state, 0x41);
+        eg_await(&m->cons_done[2], seq, m, c.state, 0x42);
     };
     auto ready = [&](unsigned seq) { eg_release(); eg_st(&m->xin_ready, seq); };
     constexpr int NPQ = LEADER ? 1 : EgUnit<EG_OP_QKV>::NP, NPO = EgUnit<EG_OP_O>::NP, NPG = LEADER ? 1 : EgUnit<EG_OP_GU>::NP, NPD = EgUnit<EG_OP_DN>::NP;
@@ -766,56 +782,62 @@ __device__ __forceinline__ void eg_consumer(EgCtx& c) {
         {
             u32x4_t pre[NPQ][16];
             if constexpr (LEADER) {
-                if (l > 0 && !others_done(s0 - 1)) return;
-                if (!eg_stage_norm(c, eg_mb(c, l, EG_MB_X), eg_epoch(c, l, 0), a.gamma + (size_t)(2 * l) * EG_D, l == 0)) return;
+                if (l > 0) others_done(s0 - 1);
+                eg_stage_norm(c, eg_mb(c, l, EG_MB_X), eg_epoch(c, l, 0), a.gamma + (size_t)(2 * l) * EG_D, l == 0);
                 ready(s0);
                 eg_stamp(c, l, 1);
             } else {
-                if (!eg_preload<EG_OP_QKV>(c, g0, pre)) return;
+                eg_preload<EG_OP_QKV>(c, g0, pre);
             }
             eg_fresh(c);
-            if (!eg_run_rows<EG_OP_QKV, LEADER>(c, g0, EG_S_QKV, l, s0, pre)) return;
+            eg_run_rows<EG_OP_QKV, LEADER>(c, g0, EG_S_QKV, l, s0, pre);
         }
         if constexpr (LEADER) eg_stamp(c, l, 2);
         eg_fresh(c);
         {
             // o_proj's first slots go into registers BEFORE the attention: the ring then takes the first gate/up slots while the attention runs
+            // Only the FIRST slot of each wave in front of the attention: when qkv ends the loader is a slot or two ahead of the consumers, so slots 27 .. 29
+            // land ~2.5 us later, and a wave that waited for them here started the attention that much later (the q / k / v granule wait of the attention
+            // CUs grew from 2.1 to 3.6 us, which ate the whole gain of the deeper hold).  They are taken inside the attention, where they have landed.
             u32x4_t pre_o[NPO][16];
-            if (!eg_preload<EG_OP_O>(c, g0 + EG_S_QKV, pre_o)) return;
+            eg_preload<EG_OP_O, NPO, 0, 1>(c, g0 + EG_S_QKV, pre_o);
+            auto rest = [&]() { eg_preload<EG_OP_O, NPO, 1, NPO>(c, g0 + EG_S_QKV, pre_o); };
             if constexpr (SPLITK) {
                 if (attn_cu) {
-                    if (split) { if (!eg_attention<MASK, LEADER, true, true>(c, l)) return; }
-                    else { if (!eg_attention<MASK, LEADER, true, false>(c, l)) return; }
-                } else if (split) { if (!eg_attention<MASK, LEADER, false, true>(c, l)) return; }
+                    if (split) eg_attention<MASK, LEADER, true, true>(c, l, rest);
+                    else eg_attention<MASK, LEADER, true, false>(c, l, rest);
+                } else if (split) eg_attention<MASK, LEADER, false, true>(c, l, rest);
+                else rest();
             } else {
-                if (attn_cu && !eg_attention<MASK, LEADER, true, false>(c, l)) return;
+                if (attn_cu) eg_attention<MASK, LEADER, true, false>(c, l, rest);
+                else rest();
             }
             eg_fresh(c);
             if constexpr (LEADER) eg_stamp(c, l, 3);
-            if (!eg_run_kmajor<EG_OP_O, LEADER>(c, g0 + EG_S_QKV, EG_S_O, l, s0 + 1, eg_mb(c, l, EG_MB_AO), eg_epoch(c, l, 2), pre_o)) return;
+            eg_run_kmajor<EG_OP_O, LEADER>(c, g0 + EG_S_QKV, EG_S_O, l, s0 + 1, eg_mb(c, l, EG_MB_AO), eg_epoch(c, l, 2), pre_o);
         }
         if constexpr (LEADER) eg_stamp(c, l, 5);
         eg_fresh(c);
         {
             u32x4_t pre[NPG][16];
             if constexpr (LEADER) {
-                if (!others_done(s0)) return;               // (qkv's readers of xin; o_proj does not touch it)
-                if (!eg_stage_norm(c, eg_mb(c, l, EG_MB_X1), eg_epoch(c, l, 3), a.gamma + (size_t)(2 * l + 1) * EG_D, false)) return;
+                others_done(s0);               // (qkv's readers of xin; o_proj does not touch it)
+                eg_stage_norm(c, eg_mb(c, l, EG_MB_X1), eg_epoch(c, l, 3), a.gamma + (size_t)(2 * l + 1) * EG_D, false);
                 ready(s0 + 2);
                 eg_stamp(c, l, 6);
             } else {
-                if (!eg_preload<EG_OP_GU>(c, g0 + EG_S_QKV + EG_S_O, pre)) return;
+                eg_preload<EG_OP_GU>(c, g0 + EG_S_QKV + EG_S_O, pre);
             }
             eg_fresh(c);
-            if (!eg_run_rows<EG_OP_GU, LEADER>(c, g0 + EG_S_QKV + EG_S_O, G.upc, l, s0 + 2, pre)) return;
+            eg_run_rows<EG_OP_GU, LEADER>(c, g0 + EG_S_QKV + EG_S_O, G.upc, l, s0 + 2, pre);
         }
         if constexpr (LEADER) eg_stamp(c, l, 7);
         eg_fresh(c);
         {
             u32x4_t pre[NPD][16];
-            if (!eg_preload<EG_OP_DN>(c, g0 + EG_S_QKV + EG_S_O + G.upc, pre)) return;
+            eg_preload<EG_OP_DN>(c, g0 + EG_S_QKV + EG_S_O + G.upc, pre);
             eg_fresh(c);
-            if (!eg_run_kmajor<EG_OP_DN, LEADER>(c, g0 + EG_S_QKV + EG_S_O + G.upc, G.s_dn, l, s0 + 3, eg_mb(c, l, EG_MB_ACT), eg_epoch(c, l, 4), pre)) return;
+            eg_run_kmajor<EG_OP_DN, LEADER>(c, g0 + EG_S_QKV + EG_S_O + G.upc, G.s_dn, l, s0 + 3, eg_mb(c, l, EG_MB_ACT), eg_epoch(c, l, 4), pre);
         }
         if constexpr (LEADER) eg_stamp(c, l, 9);
     }
@@ -825,20 +847,20 @@ __device__ __forceinline__ void eg_consumer(EgCtx& c) {
     {
         u32x4_t pre[NPQ][16];
         if constexpr (LEADER) {
-            if (!others_done(sl - 1)) return;
-            if (!eg_stage_norm(c, eg_mb(c, L, EG_MB_X), eg_epoch(c, L, 0), a.gamma + (size_t)(2 * L) * EG_D, false)) return;
+            others_done(sl - 1);
+            eg_stage_norm(c, eg_mb(c, L, EG_MB_X), eg_epoch(c, L, 0), a.gamma + (size_t)(2 * L) * EG_D, false);
             ready(sl);
         } else {
-            if (!eg_preload<EG_OP_LM>(c, L * G.slots_layer, pre)) return;
+            eg_preload<EG_OP_LM>(c, L * G.slots_layer, pre);
         }
         eg_fresh(c);
-        if (!eg_run_rows<EG_OP_LM, LEADER>(c, L * G.slots_layer, G.s_lm, L, sl, pre)) return;
+        eg_run_rows<EG_OP_LM, LEADER>(c, L * G.slots_layer, G.s_lm, L, sl, pre);
     }
     if constexpr (LEADER) {
         if (a.tail_ids_out) {
-            if (!others_done(sl)) return;
+            others_done(sl);
             eg_acquire();
-            if (!eg_greedy_tail(c, L)) return;
+            eg_greedy_tail(c, L);
         }
         // the launch sequence number moves on once per successful launch (every workgroup read it before its first publish, and this store sits
         // behind the last all-gather, which needed all of them)
